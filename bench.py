@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native OpenPano hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--texture synthetic|natural]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--texture synthetic|natural] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 and no torch.distributed environment re-executes itself under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` (one
@@ -69,6 +69,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaled config-4 section")
     ap.add_argument("--no-e2e", action="store_true", help="skip the whole-pipeline (ESTIMATE_CAMERA) section")
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2, 3 and 4_natural (N = 1 sections)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's descriptors and keypoint coordinates) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -476,6 +478,34 @@ def run_blend(hip, ctx, cfg, inputs, H, W, args, log):
     return res
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(feats, out_dir, log):
+    """The timed step's result as a caller of op_sift_batch receives it: per image (in image order) the descriptors
+    (K x 128 fp32) and keypoint coordinates (K x 2 fp64), concatenated.  Above DUMP_CAP_BYTES a fixed, seeded sample of
+    rows is written instead, its row numbers in sample_rows.npy."""
+    import numpy as np
+    n = feats.num_images
+    got = [feats.get(i) for i in range(n)]
+    desc = np.concatenate([d for d, _ in got]) if n else np.zeros((0, 128), np.float32)
+    coor = np.concatenate([c for _, c in got]) if n else np.zeros((0, 2), np.float64)
+    counts = np.array([len(d) for d, _ in got], np.float64)
+    row_bytes = desc.itemsize * 128 + coor.itemsize * 2 + 8
+    cap_rows = (DUMP_CAP_BYTES - counts.nbytes - 4096) // row_bytes         # (4096: the .npy headers)
+    arrays = {"keypoints_per_image": counts}
+    if len(desc) > cap_rows:
+        rows = np.sort(np.random.default_rng(0).choice(len(desc), cap_rows, replace=False))
+        desc, coor = desc[rows], coor[rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    arrays["descriptors"] = desc
+    arrays["coordinates"] = coor
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {tuple(a.shape)} {a.dtype}" for k, a in arrays.items()))
+
+
 def config4_views(args, rank, world, log):
     """-> (all views of the sets this rank needs, local image list, n_total, description)"""
     from openpano_amd import synth
@@ -594,6 +624,8 @@ def main():
     t_sift = time.perf_counter() - t0
     prof = ctx.profile()
     ctx.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(feats, args.dump_outputs, log)
     k_rank = int(feats.total)
     tt = torch.tensor([t_sift, float(k_rank)], dtype=torch.float64, device=dev)
     if dist is not None:

@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 def test_bench_cli_declares_the_contract_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--scaling"):
+    for flag in ("--gpus", "--steps", "--warmup", "--scaling", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -34,6 +34,44 @@ def test_bench_gpus_n_spawns_its_own_ranks():
     # every rank fails there; the launcher may end the second rank before its message is out (seen once under load): one is proof enough
     assert out.stderr.count("op_ctx_create: no HIP device available") >= 1, out.stderr[-2000:]
     assert "launch multi-GPU runs with" not in out.stderr
+
+
+class _FakeFeatures:
+    """the part of hip.Features that bench.dump_outputs reads"""
+
+    def __init__(self, counts):
+        self.counts = counts
+        self.num_images = len(counts)
+
+    def get(self, i):
+        r = np.random.default_rng(i)
+        return r.random((self.counts[i], 128), dtype=np.float32), r.random((self.counts[i], 2))
+
+
+def test_dump_outputs_writes_the_step_result(tmp_path):
+    """--dump-outputs: descriptors / coordinates of every image, concatenated in image order, float32 / float64."""
+    import bench
+    f = _FakeFeatures([5, 0, 7])
+    bench.dump_outputs(f, str(tmp_path), lambda m: None)
+    d, c, k = (np.load(tmp_path / (n + ".npy")) for n in ("descriptors", "coordinates", "keypoints_per_image"))
+    assert d.dtype == np.float32 and c.dtype == np.float64 and k.dtype == np.float64
+    assert np.array_equal(d, np.concatenate([f.get(i)[0] for i in range(3)]))
+    assert np.array_equal(c, np.concatenate([f.get(i)[1] for i in range(3)]))
+    assert k.tolist() == [5, 0, 7] and not (tmp_path / "sample_rows.npy").exists()
+
+
+def test_dump_outputs_samples_above_the_cap(tmp_path, monkeypatch):
+    """Above the cap a fixed seeded sample of rows is written (the same rows every time), its row numbers next to it."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 64 << 10)
+    f = _FakeFeatures([300, 200])
+    full = np.concatenate([f.get(i)[0] for i in range(2)])
+    for sub in ("a", "b"):
+        bench.dump_outputs(f, str(tmp_path / sub), lambda m: None)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")) <= 64 << 10
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert 0 < len(rows) < 500 and np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "descriptors.npy"), full[rows.astype(np.int64)])
 
 
 def test_pyramid_pixels_matches_the_oracle_plan(oracle, cfg):
