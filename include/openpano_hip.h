@@ -343,6 +343,36 @@ int op_canvas_crop(op_ctx* ctx, const op_canvas* c, op_canvas** out, int* x0, in
  * truncated to a byte; D2H of H x W x 3 bytes instead of the fp32 canvas */
 int op_canvas_copy_u8(op_ctx* ctx, const op_canvas* c, unsigned char* host);
 
+/* ---- EXPOSURE (GAIN) COMPENSATION -- an extension beyond the reference, which asks for fixed exposure instead (README,
+ * Quality Guidelines): the gain compensation of Brown & Lowe, "Automatic Panoramic Image Stitching using Invariant
+ * Features" (IJCV 2007, section 6).  Opt-in: op_blend itself is unchanged.
+ *
+ * Pairs (a < b) of n images are stored at index  a*n - a*(a+1)/2 + (b - a - 1),  n*(n-1)/2 entries.
+ *
+ * op_gain_overlap: overlap statistics over the canvas op_blend would produce, on the lattice of canvas pixels whose row and
+ * column are multiples of `stride` (>= 1).  At each such pixel every image whose sample is valid by the LINEAR blender's
+ * rules (cfg->LAZY_READ's ROI test, map_coor bounds, interpolate() != NO, col[0] >= 0 -- whatever cfg->MULTIBAND says)
+ * takes part; for every pair (a < b) of them: count[p] += 1, sums[6p + c] += col_a[c], sums[6p + 3 + c] += col_b[c]
+ * (c = 0..2), colours in fixed point llrint(col * 2^32) summed in int64: the result does not depend on the order of the
+ * device's additions (bit-equal between runs).  Images are expected in [0, 1].  count / sums may be NULL when n == 1.
+ * At most 262144 images (OP_ERR_UNSUPPORTED beyond).
+ * op_gain_solve (HOST ONLY, no device): the gains minimising
+ *   e = 1/2 sum_a sum_{b!=a} N_ab [ (g_a I_ab - g_b I_ba)^2 / sigma_n^2 + (1 - g_a)^2 / sigma_g^2 ],  I_ab = S_ab / (2^32 N_ab),
+ * intensities in [0, 1] units (usual sigma_n = 10/255, sigma_g = 0.1).  per_channel = 1: one solve per channel;
+ * 0: one solve on the grey mean (S[0]+S[1]+S[2]) / 3, the same gain for all three channels.  An image without overlap
+ * gets 1.  gains: n x 3.
+ * op_blend_gains: op_blend with every valid sample scaled, col[c] = min(col[c] * gains[3k + c], 1) -- in the linear
+ * blender and in the multiband blender's level 0 -- where a channel whose gain is exactly 1 is left as it is.  gains:
+ * n x 3 host floats, finite and > 0; NULL = op_blend.  All-ones gains give op_blend's canvas bit for bit.
+ * Bad arguments (NULLs, n < 1, stride < 1, non-positive or non-finite sigmas / gains) return OP_ERR_INVALID.
+ * Threading and ownership as op_blend: one call at a time per context; the caller owns count / sums / gains and the
+ * returned canvas (op_canvas_free). */
+int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
+		int64_t* count, int64_t* sums);
+int op_gain_solve(int n, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, int per_channel, float* gains);
+int op_blend_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n,
+		const float* gains, op_canvas** out);
+
 /* CYLINDER mode pre-warp -- replaces CylinderWarper::warp (stitch/warp.hh:47-55, warp.cc:13-75).
  * op_cyl_warp_shape is the host part (projector, output shape, offset and the keypoints, which
  * are centred coordinates updated in place: warp.cc:46-67); op_cyl_warp renders the pixels. */

@@ -133,9 +133,36 @@ __device__ __forceinline__ void walk_cover(const unsigned long long* s_cover, in
 	}
 }
 
-// ---- LinearBlender::run (blender.cc:24-96): thread per canvas pixel, images in index order ----
+// One sample of LinearBlender::run (blender.cc:26-36, GET_COLOR_AND_W without the weight) at canvas pixel (i, j):
+// the ROI test of the branch (non-lazy: Range::contain, inclusive, blender.cc:84; lazy: the loops exclude max,
+// blender.cc:49-51), ImageToAdd::map_coor (blender.hh:39-44), interpolate() != NO and col[0] >= 0.  false = the image
+// adds nothing here.  r / c: the sample's image coordinates (the blend weight's operands).
+__device__ __forceinline__ bool linear_sample(const BlendImg& im, int i, int j, double hx, double hy, double hz, int lazy,
+		float& r, float& c, float (&col)[3]) {
+	const bool in = lazy ? (i >= im.y0 && i < im.y1 && j >= im.x0 && j < im.x1)
+	                     : (i >= im.y0 && i <= im.y1 && j >= im.x0 && j <= im.x1);
+	if (!in) return false;
+	double ox, oy;
+	space_to_image(im, hx, hy, hz, ox, oy);
+	if (ox < 0 || ox >= im.w || oy < 0 || oy >= im.h) return false;
+	r = (float)oy; c = (float)ox;
+	if (!interpolate(im.data, im.mh, im.mw, r, c, col)) return false;
+	return !(col[0] < 0);
+}
+
+// Exposure gain of a valid sample (op_blend_gains): col * g clamped to 1, so a gained colour stays in [0, 1] (Color::NO,
+// multiband's final clamp and write_rgb's truncation keep their meaning).  A channel whose gain is exactly 1 is left
+// untouched: bilinear weights can sum one ulp above 1, and a clamp there would move the pixel off op_blend's.
+__device__ __forceinline__ void apply_gain(const float* __restrict__ g, float (&col)[3]) {
+#pragma unroll
+	for (int ch = 0; ch < 3; ++ch) { const float gc = g[ch]; if (gc != 1.f) col[ch] = fminf(col[ch] * gc, 1.f); }
+}
+
+// ---- LinearBlender::run (blender.cc:24-96): thread per canvas pixel, images in index order.  GAIN: gains (n x 3)
+// scale every sample (op_blend_gains); without it the kernel is op_blend's ----
+template <bool GAIN>
 __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
-		float* __restrict__ out, int H, int W, int ordered_input, int lazy) {
+		float* __restrict__ out, int H, int W, int ordered_input, int lazy, const float* __restrict__ gains) {
 	__shared__ unsigned long long s_cover[COVER_WORDS];
 	const int j = blockIdx.x * 64 + (threadIdx.x & 63);
 	const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -148,17 +175,9 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 		if (!live) continue;
 		walk_cover(s_cover, k0, n, [&](int k) {
 			const BlendImg& im = imgs[k];
-			// non-lazy: Range::contain, inclusive (blender.cc:84); lazy: loops exclude max (blender.cc:49-51)
-			const bool in = lazy ? (i >= im.y0 && i < im.y1 && j >= im.x0 && j < im.x1)
-			                     : (i >= im.y0 && i <= im.y1 && j >= im.x0 && j <= im.x1);
-			if (!in) return;
-			double ox, oy;
-			space_to_image(im, hx, hy, hz, ox, oy);
-			if (ox < 0 || ox >= im.w || oy < 0 || oy >= im.h) return;      // ImageToAdd::map_coor (blender.hh:39-44)
-			const float r = (float)oy, c = (float)ox;
-			float col[3];
-			if (!interpolate(im.data, im.mh, im.mw, r, c, col)) return;
-			if (col[0] < 0) return;
+			float r, c, col[3];
+			if (!linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col)) return;
+			if (GAIN) apply_gain(gains + 3 * (long long)k, col);
 			float w = (float)(0.5 - fabs((double)(c / (float)im.w) - 0.5));
 			if (!ordered_input) w = (float)((double)w * (0.5 - fabs((double)(r / (float)im.h) - 0.5)));
 			s0 += col[0] * w; s1 += col[1] * w; s2 += col[2] * w;
@@ -178,6 +197,110 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 	}
 }
 
+// ---- exposure statistics (Brown & Lowe, IJCV 2007, section 6) for op_gain_overlap: thread per point of the canvas
+// lattice (i, j) = (ti, tj) * stride; at every point, the samples of the linear blender (linear_sample: same map, same
+// validity rules, same interpolation) of every covering image, and for every pair (a < b) of valid samples
+// N_ab += 1, S_ab[c] += col_a[c], S_ba[c] += col_b[c].  Colours are summed in fixed point, llrint(col * 2^32) as int64
+// (exact scaling; integer addition is associative, so the sums do not depend on the order the hardware adds them in):
+// a pair's sums are reduced across the wavefront (a row of 64 lattice points), then one 64-bit atomic per value.
+// The workgroup's cover set -- images whose ROI meets its 64 x 4 tile of lattice points -- is ONE bitmask over all n
+// images (dynamic LDS, ceil(n / 64) words), so pairs may straddle any 64-image word.  It is walked in chunks of
+// GAIN_CH images whose samples stay in registers (fully unrolled: constant indices, no scratch); the pairs of a chunk
+// with itself, then with every later covered image, one at a time.  A tile is usually covered by <= 4 images: one
+// chunk, every image sampled once.
+constexpr int GAIN_CH = 8;
+constexpr double GAIN_FIX = 4294967296.0;       // 2^32
+constexpr int GAIN_MAX_IMAGES = 64 * 4096;       // cover bitmask: 4096 words = 32 KB of LDS
+// smallest covered image index >= k (k wave-uniform), or words * 64 when there is none; wave-uniform
+__device__ __forceinline__ int next_cover(const unsigned long long* s_cover, int words, int k) {
+	for (int wd = k >> 6; wd < words; ++wd) {
+		unsigned long long m = s_cover[wd];
+		if (wd == (k >> 6)) m &= ~0ull << (k & 63);
+		const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m), hi = __builtin_amdgcn_readfirstlane((unsigned)(m >> 32));
+		if (lo) return wd * 64 + __builtin_ctz(lo);
+		if (hi) return wd * 64 + 32 + __builtin_ctz(hi);
+	}
+	return words * 64;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+	return v;
+}
+// pair (a < b) at a * n - a (a + 1) / 2 + (b - a - 1) (include/openpano_hip.h); x / y: the samples of a / b, valid as
+// linear_sample said (va / vb)
+__device__ __forceinline__ void gain_pair(int a, int b, int n, bool va, const float (&x)[3], bool vb, const float (&y)[3],
+		unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+	const bool both = va && vb;
+	const unsigned long long bal = __ballot(both);
+	if (!bal) return;                                   // wave-uniform
+	long long v[6];
+#pragma unroll
+	for (int ch = 0; ch < 3; ++ch) {
+		v[ch] = both ? llrint((double)x[ch] * GAIN_FIX) : 0;
+		v[3 + ch] = both ? llrint((double)y[ch] * GAIN_FIX) : 0;
+	}
+#pragma unroll
+	for (int q = 0; q < 6; ++q) v[q] = wave_sum(v[q]);
+	if ((threadIdx.x & 63) == 0) {
+		const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+		atomicAdd(count + p, (unsigned long long)__popcll(bal));
+#pragma unroll
+		for (int q = 0; q < 6; ++q) atomicAdd(sums + 6 * p + q, (unsigned long long)v[q]);
+	}
+}
+__global__ void __launch_bounds__(256) k_gain_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
+		int H, int W, int stride, int lazy, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+	extern __shared__ unsigned long long s_gcover[];
+	const int words = (n + 63) >> 6;
+	const int i = (blockIdx.y * 4 + (threadIdx.x >> 6)) * stride;
+	const int j = (blockIdx.x * 64 + (threadIdx.x & 63)) * stride;
+	const bool live = i < H && j < W;
+	{	// tile_cover over all n images at once; the tile spans 3 * stride rows and 63 * stride columns of the canvas
+		const int i0 = blockIdx.y * 4 * stride, j0 = blockIdx.x * 64 * stride, excl = lazy ? 1 : 0;
+		for (int k = (int)threadIdx.x; k < words * 64; k += 256) {
+			bool hit = false;
+			if (k < n) {
+				const BlendImg& im = imgs[k];
+				hit = im.x0 <= j0 + 63 * stride && im.x1 - excl >= j0 && im.y0 <= i0 + 3 * stride && im.y1 - excl >= i0;
+			}
+			const unsigned long long b = __ballot(hit);
+			if ((threadIdx.x & 63) == 0) s_gcover[k >> 6] = b;
+		}
+		__syncthreads();
+	}
+	double hx, hy, hz;
+	proj2homo(g, trig, i, j, hx, hy, hz);
+	auto sample = [&](int k, float (&col)[3]) -> bool {
+		float r, c;
+		return live && linear_sample(imgs[k], i, j, hx, hy, hz, lazy, r, c, col);
+	};
+	int a0 = next_cover(s_gcover, words, 0);
+	while (a0 < n) {
+		int ka[GAIN_CH]; bool va[GAIN_CH]; float ca[GAIN_CH][3];
+		int k = a0;
+#pragma unroll
+		for (int s = 0; s < GAIN_CH; ++s) {
+			ka[s] = k;
+			va[s] = false;
+			if (k < n) { va[s] = sample(k, ca[s]); k = next_cover(s_gcover, words, k + 1); }
+		}
+#pragma unroll
+		for (int s = 0; s < GAIN_CH; ++s)
+#pragma unroll
+			for (int t = s + 1; t < GAIN_CH; ++t)
+				if (ka[t] < n) gain_pair(ka[s], ka[t], n, va[s], ca[s], va[t], ca[t], count, sums);
+		const int a1 = k;                               // first covered image after this chunk
+		for (int b = a1; b < n; b = next_cover(s_gcover, words, b + 1)) {
+			float cb[3];
+			const bool vb = sample(b, cb);
+#pragma unroll
+			for (int s = 0; s < GAIN_CH; ++s) gain_pair(ka[s], b, n, va[s], ca[s], vb, cb, count, sums);
+		}
+		a0 = a1;
+	}
+}
+
 // ---- create_first_level + update_weight_map (multiband.cc:19-56,125-143) in ONE pass, thread per canvas pixel:
 // proj2homo once per pixel (it does not depend on the image), then every image whose ROI covers the pixel in index
 // order: its level-0 WeightedPixel is written with weight 0 while the winner of the winner-takes-all map -- the first
@@ -185,8 +308,11 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 // the winner's weight is then set to 1 with one 4-byte store.  The ROI planes are written once and never read back
 // (the two-kernel form re-read every weight and rewrote it: 0.49 GB of the 1.33 GB the two kernels moved), and the
 // target canvas / its "seen" mask are initialised here too (fill(target, Color::NO), multiband.cc:60-61).
+// GAIN: the level-0 colours are the gained samples (op_blend_gains); the weights do not depend on colour.
+template <bool GAIN>
 __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
-		float4* __restrict__ cur, unsigned char* __restrict__ mask, float* __restrict__ out, unsigned char* __restrict__ tmask, int H, int W) {
+		float4* __restrict__ cur, unsigned char* __restrict__ mask, float* __restrict__ out, unsigned char* __restrict__ tmask, int H, int W,
+		const float* __restrict__ gains) {
 	const int j = blockIdx.x * 64 + (threadIdx.x & 63);
 	const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
 	// The target is as large as the largest bottom-right ROI coordinate (blender.cc:21) while ROIs are inclusive
@@ -211,6 +337,7 @@ __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig t
 			float col[3];
 			bool ok = interpolate(im.data, im.mh, im.mw, (float)oy, (float)ox, col);
 			if (ok) { float mn = fminf(col[0], fminf(col[1], col[2])); if (mn < 0) ok = false; }
+			if (GAIN && ok) apply_gain(gains + 3 * (long long)k, col);
 			float4 px = make_float4(0.f, 0.f, 0.f, 0.f);
 			if (ok) {
 				const double x = ox / (double)im.w - 0.5, y = oy / (double)im.h - 0.5;
@@ -814,26 +941,24 @@ int op_blend_canvas_dims(const op_blend_geom* g, const op_blend_image* imgs, int
 	return OP_OK;
 }
 
-int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, op_canvas** out) {
-	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend: bad argument");
-	if (g->proj_method < 0 || g->proj_method > 2) OP_FAIL(OP_ERR_INVALID, "op_blend: bad projection method");
-	if (!(g->resolution[0] > 0) || !(g->resolution[1] > 0)) OP_FAIL(OP_ERR_INVALID, "op_blend: resolution must be positive");
-	HIPCHK(hipSetDevice(ctx->device));
+}	// extern "C"
+
+namespace {
+// The op_blend_image array on the device as BlendImg (host images are uploaded; the uploads are freed with fr).  `who`
+// prefixes the error messages.
+int upload_images(op_ctx* ctx, const char* who, const op_blend_geom* g, const op_blend_image* imgs, int n, Freer& fr,
+		std::vector<BlendImg>& h_imgs, long long& roi_total, long long& max_roi, BlendImg** d_out) {
 	hipStream_t st = ctx->stream;
-	int H, W;
-	int rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
-	if (rc != OP_OK) return rc;
-	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, "op_blend: empty canvas");
-	Freer fr;
-	std::vector<BlendImg> h_imgs(n);
-	long long roi_total = 0; long long max_roi = 0;
+	const std::string w = who;
+	h_imgs.assign(n, BlendImg{});
+	roi_total = 0; max_roi = 0;
 	for (int k = 0; k < n; ++k) {
 		const op_blend_image& s = imgs[k];
-		if (!s.data || s.h < 2 || s.w < 2) OP_FAIL(OP_ERR_INVALID, "op_blend: bad image " + std::to_string(k));
+		if (!s.data || s.h < 2 || s.w < 2) OP_FAIL(OP_ERR_INVALID, w + ": bad image " + std::to_string(k));
 		BlendImg& b = h_imgs[k];
 		b.h = s.h; b.w = s.w;
 		b.mh = s.mat_h > 0 ? s.mat_h : s.h; b.mw = s.mat_w > 0 ? s.mat_w : s.w;
-		if (b.mh < 2 || b.mw < 2) OP_FAIL(OP_ERR_INVALID, "op_blend: bad pixel buffer size of image " + std::to_string(k));
+		if (b.mh < 2 || b.mw < 2) OP_FAIL(OP_ERR_INVALID, w + ": bad pixel buffer size of image " + std::to_string(k));
 		if (s.on_device) b.data = s.data;
 		else {
 			float* d = nullptr;
@@ -842,7 +967,7 @@ int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op
 			b.data = d;
 		}
 		int roi[4]; roi_of(g, s.range, roi);
-		if (roi[0] < 0 || roi[1] < 0 || roi[2] < roi[0] || roi[3] < roi[1]) OP_FAIL(OP_ERR_INVALID, "op_blend: image range outside proj_range");
+		if (roi[0] < 0 || roi[1] < 0 || roi[2] < roi[0] || roi[3] < roi[1]) OP_FAIL(OP_ERR_INVALID, w + ": image range outside proj_range");
 		b.x0 = roi[0]; b.y0 = roi[1]; b.x1 = roi[2]; b.y1 = roi[3];
 		memcpy(b.hinv, s.homo_inv, sizeof(b.hinv));
 		b.rw = roi[2] - roi[0] + 1; b.rh = roi[3] - roi[1] + 1;      // Range::width/height, inclusive
@@ -852,22 +977,55 @@ int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op
 	BlendImg* d_imgs = nullptr;
 	HIPCHK(pool_alloc((void**)&d_imgs, sizeof(BlendImg) * n)); fr.v.push_back(d_imgs);
 	HIPCHK(hipMemcpyAsync(d_imgs, h_imgs.data(), sizeof(BlendImg) * n, hipMemcpyHostToDevice, st));
+	*d_out = d_imgs;
+	return OP_OK;
+}
+
+int check_blend_args(const char* who, const op_blend_geom* g) {
+	if (g->proj_method < 0 || g->proj_method > 2) OP_FAIL(OP_ERR_INVALID, std::string(who) + ": bad projection method");
+	if (!(g->resolution[0] > 0) || !(g->resolution[1] > 0)) OP_FAIL(OP_ERR_INVALID, std::string(who) + ": resolution must be positive");
+	return OP_OK;
+}
+
+// op_blend (gains == NULL) and op_blend_gains (gains: n x 3 on the host)
+int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
+		const char* who, op_canvas** out) {
+	int rc = check_blend_args(who, g);
+	if (rc != OP_OK) return rc;
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	int H, W;
+	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
+	if (rc != OP_OK) return rc;
+	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, std::string(who) + ": empty canvas");
+	Freer fr;
+	std::vector<BlendImg> h_imgs;
+	long long roi_total = 0, max_roi = 0;
+	BlendImg* d_imgs = nullptr;
+	rc = upload_images(ctx, who, g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
+	if (rc != OP_OK) return rc;
+	float* d_gains = nullptr;
+	if (gains) {
+		HIPCHK(pool_alloc((void**)&d_gains, sizeof(float) * 3 * (size_t)n)); fr.v.push_back(d_gains);
+		HIPCHK(hipMemcpyAsync(d_gains, gains, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+	}
 	op_canvas* cv = new op_canvas;
 	cv->h = H; cv->w = W; cv->device = ctx->device;
-	if (pool_alloc((void**)&cv->data, sizeof(float) * 3 * (size_t)H * W) != hipSuccess) { delete cv; OP_FAIL(OP_ERR_HIP, "op_blend: canvas allocation failed"); }
+	if (pool_alloc((void**)&cv->data, sizeof(float) * 3 * (size_t)H * W) != hipSuccess) { delete cv; OP_FAIL(OP_ERR_HIP, std::string(who) + ": canvas allocation failed"); }
 	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
 	const dim3 cgrid((W + 63) / 64, (H + 3) / 4);
 	BlendTrig trig{nullptr, nullptr, 0, 0};
 	if (bg.method != 0) {
 		HostScope hs(ctx, "blend trig tables (host)");
 		hipError_t e = trig_tables(ctx, bg, W + 1, H + 1, &trig);
-		if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string("op_blend: trig tables: ") + hipGetErrorString(e)); }
+		if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string(who) + ": trig tables: " + hipGetErrorString(e)); }
 	}
 #define BCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
 	pool_free(cv->data); delete cv; return OP_ERR_HIP; } } while (0)
 	if (cfg->MULTIBAND <= 0) {
 		ProfScope ps(ctx, "blend linear");
-		hipLaunchKernelGGL(k_blend_linear, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ);
+		if (d_gains) hipLaunchKernelGGL(k_blend_linear<true>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains);
+		else hipLaunchKernelGGL(k_blend_linear<false>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, nullptr);
 		BCHK(hipGetLastError());
 	} else {
 		const int L = cfg->MULTIBAND;
@@ -883,7 +1041,9 @@ int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op
 		BCHK(pool_alloc((void**)&tmask, (size_t)H * W)); fr.v.push_back(tmask);
 		const dim3 rgrid((unsigned)((max_roi + 255) / 256), n);
 		{ ProfScope ps(ctx, "multiband first level");
-		  hipLaunchKernelGGL(k_mb_first_fused, dim3((W + 1 + 63) / 64, (H + 1 + 3) / 4), dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W);
+		  const dim3 fgrid((W + 1 + 63) / 64, (H + 1 + 3) / 4);
+		  if (d_gains) hipLaunchKernelGGL(k_mb_first_fused<true>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains);
+		  else hipLaunchKernelGGL(k_mb_first_fused<false>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, nullptr);
 		  BCHK(hipGetLastError()); }
 		bool band0_done = false;                 // level 0's band written by the fused blur
 		for (int level = 0; level < L; ++level) {
@@ -895,7 +1055,7 @@ int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op
 				ProfScope ps(ctx, "multiband blur");
 				BlurTaps taps; memset(&taps, 0, sizeof(taps));
 				if (gauss_taps((float)(std::sqrt(level * 2 + 1.0) * 4), cfg->GAUSS_WINDOW_FACTOR, taps) != 0) {
-					pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_UNSUPPORTED, "op_blend: Gaussian kernel wider than 31 taps");
+					pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_UNSUPPORTED, std::string(who) + ": Gaussian kernel wider than 31 taps");
 				}
 				if (taps.center == 6 || taps.center == 9) {       // shipped GAUSS_WINDOW_FACTOR: both passes in one kernel
 					const int C = taps.center, two = 256 - 2 * C, segr = (C <= 6 ? 8 : 6) * (2 * C + 2);      // k_mb_blur_fused: SEG
@@ -937,6 +1097,148 @@ int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op
 #undef BCHK
 	resolve_profile(ctx);
 	*out = cv;
+	return OP_OK;
+}
+
+}	// namespace
+
+extern "C" {
+
+int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, op_canvas** out) {
+	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend: bad argument");
+	return blend_impl(ctx, cfg, g, imgs, n, nullptr, "op_blend", out);
+}
+
+int op_blend_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains, op_canvas** out) {
+	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend_gains: bad argument");
+	if (gains)
+		for (int e = 0; e < 3 * n; ++e)
+			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
+				OP_FAIL(OP_ERR_INVALID, "op_blend_gains: gain " + std::to_string(e) + " (image " + std::to_string(e / 3) + ") is not finite and positive");
+	return blend_impl(ctx, cfg, g, imgs, n, gains, "op_blend_gains", out);
+}
+
+int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
+		int64_t* count, int64_t* sums) {
+	if (!ctx || !cfg || !g || !imgs || n < 1 || stride < 1 || (n > 1 && (!count || !sums)))
+		OP_FAIL(OP_ERR_INVALID, "op_gain_overlap: bad argument");
+	int rc = check_blend_args("op_gain_overlap", g);
+	if (rc != OP_OK) return rc;
+	const int words = (n + 63) / 64;
+	if (words > GAIN_MAX_IMAGES / 64) OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
+	const long long npairs = (long long)n * (n - 1) / 2;
+	if (npairs == 0) return OP_OK;
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	int H, W;
+	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
+	if (rc != OP_OK) return rc;
+	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, "op_gain_overlap: empty canvas");
+	Freer fr;
+	std::vector<BlendImg> h_imgs;
+	long long roi_total = 0, max_roi = 0;
+	BlendImg* d_imgs = nullptr;
+	rc = upload_images(ctx, "op_gain_overlap", g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
+	if (rc != OP_OK) return rc;
+	unsigned long long* d_stats = nullptr;         // npairs counts, then npairs x 6 sums
+	const size_t stat_bytes = sizeof(unsigned long long) * 7 * (size_t)npairs;
+	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
+	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
+	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
+	BlendTrig trig{nullptr, nullptr, 0, 0};
+	if (bg.method != 0) {            // the blend's own tables (same key: canvas + 1), so a following blend finds them cached
+		HostScope hs(ctx, "blend trig tables (host)");
+		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
+	}
+	// a stride beyond the canvas leaves the lattice {(0, 0)} -- clamped so that lattice coordinates stay far from overflow
+	stride = std::min(stride, std::max(H, W));
+	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
+	{ ProfScope ps(ctx, "gain overlap");
+	  hipLaunchKernelGGL(k_gain_overlap, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * words, st,
+	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, d_stats, d_stats + npairs);
+	  HIPCHK(hipGetLastError()); }
+	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)npairs, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(sums, d_stats + npairs, sizeof(int64_t) * 6 * (size_t)npairs, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	resolve_profile(ctx);
+	return OP_OK;
+}
+
+// Gain compensation (Brown & Lowe, IJCV 2007, section 6), host only: minimise
+//   e = 1/2 sum_a sum_{b != a} N_ab [ (g_a I_ab - g_b I_ba)^2 / sigma_n^2 + (1 - g_a)^2 / sigma_g^2 ]
+// through its normal equations (for every a, over b != a)
+//   sum_b N_ab [ (2 I_ab^2 / sigma_n^2 + 1 / sigma_g^2) g_a - (2 I_ab I_ba / sigma_n^2) g_b ] = sum_b N_ab / sigma_g^2,
+// I_ab = S_ab / (2^32 N_ab) the mean of image a over its overlap with b.  The matrix is symmetric and, for sigma_g > 0,
+// positive definite on the images with any overlap; those without are g = 1 and left out.  Cholesky, fp64, fixed loop
+// order: the gains are a function of the statistics alone.
+int op_gain_solve(int n, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, int per_channel, float* gains) {
+	if (n < 1 || !gains || (n > 1 && (!count || !sums)) || !(sigma_n > 0) || !(sigma_g > 0) || !std::isfinite(sigma_n) || !std::isfinite(sigma_g) ||
+			(per_channel != 0 && per_channel != 1))
+		OP_FAIL(OP_ERR_INVALID, "op_gain_solve: bad argument");
+	const long long npairs = (long long)n * (n - 1) / 2;
+	for (long long p = 0; p < npairs; ++p)
+		if (count[p] < 0) OP_FAIL(OP_ERR_INVALID, "op_gain_solve: negative overlap count at pair " + std::to_string(p));
+	// the active images (any overlap), in index order
+	std::vector<int> slot(n, -1), act;
+	for (int a = 0; a < n; ++a)
+		for (int b = a + 1; b < n; ++b)
+			if (count[(long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1)] > 0) { slot[a] = slot[b] = 0; }
+	for (int a = 0; a < n; ++a) if (slot[a] == 0) { slot[a] = (int)act.size(); act.push_back(a); }
+	const int m = (int)act.size();
+	for (int e = 0; e < 3 * n; ++e) gains[e] = 1.f;
+	if (m == 0) return OP_OK;
+	const double inv_n2 = 1.0 / (sigma_n * sigma_n), inv_g2 = 1.0 / (sigma_g * sigma_g);
+	std::vector<double> A((size_t)m * m), rhs(m);
+	const int nsolve = per_channel ? 3 : 1;
+	for (int ch = 0; ch < nsolve; ++ch) {
+		std::fill(A.begin(), A.end(), 0.0); std::fill(rhs.begin(), rhs.end(), 0.0);
+		for (int a = 0; a < n; ++a)
+			for (int b = a + 1; b < n; ++b) {
+				const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+				if (count[p] <= 0) continue;
+				const double N = (double)count[p], den = GAIN_FIX * N;
+				const int64_t* S = sums + 6 * p;
+				double Iab, Iba;
+				if (per_channel) { Iab = (double)S[ch] / den; Iba = (double)S[3 + ch] / den; }
+				else { Iab = ((double)(S[0] + S[1] + S[2]) / 3.0) / den; Iba = ((double)(S[3] + S[4] + S[5]) / 3.0) / den; }
+				const int sa = slot[a], sb = slot[b];
+				A[(size_t)sa * m + sa] += N * (2.0 * Iab * Iab * inv_n2 + inv_g2);
+				A[(size_t)sb * m + sb] += N * (2.0 * Iba * Iba * inv_n2 + inv_g2);
+				const double off = N * (2.0 * Iab * Iba * inv_n2);
+				A[(size_t)sa * m + sb] -= off;
+				A[(size_t)sb * m + sa] -= off;
+				rhs[sa] += N * inv_g2;
+				rhs[sb] += N * inv_g2;
+			}
+		// A = L L^T in place (lower triangle), then L y = rhs, L^T g = y
+		for (int j = 0; j < m; ++j) {
+			double d = A[(size_t)j * m + j];
+			for (int k = 0; k < j; ++k) d -= A[(size_t)j * m + k] * A[(size_t)j * m + k];
+			if (!(d > 0)) OP_FAIL(OP_ERR_INVALID, "op_gain_solve: system not positive definite (inconsistent statistics)");
+			const double l = std::sqrt(d);
+			A[(size_t)j * m + j] = l;
+			for (int i = j + 1; i < m; ++i) {
+				double v = A[(size_t)i * m + j];
+				for (int k = 0; k < j; ++k) v -= A[(size_t)i * m + k] * A[(size_t)j * m + k];
+				A[(size_t)i * m + j] = v / l;
+			}
+		}
+		for (int i = 0; i < m; ++i) {
+			double v = rhs[i];
+			for (int k = 0; k < i; ++k) v -= A[(size_t)i * m + k] * rhs[k];
+			rhs[i] = v / A[(size_t)i * m + i];
+		}
+		for (int i = m - 1; i >= 0; --i) {
+			double v = rhs[i];
+			for (int k = i + 1; k < m; ++k) v -= A[(size_t)k * m + i] * rhs[k];
+			rhs[i] = v / A[(size_t)i * m + i];
+		}
+		for (int i = 0; i < m; ++i) {
+			const float gv = (float)rhs[i];
+			if (per_channel) gains[3 * act[i] + ch] = gv;
+			else gains[3 * act[i]] = gains[3 * act[i] + 1] = gains[3 * act[i] + 2] = gv;
+		}
+	}
 	return OP_OK;
 }
 

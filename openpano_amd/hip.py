@@ -198,6 +198,12 @@ def lib():
     L.op_canvas_free.argtypes = [C.c_void_p]
     L.op_canvas_crop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.op_canvas_copy_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "op_gain_overlap"):
+        L.op_gain_overlap.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p]
+        L.op_gain_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]
+        L.op_blend_gains.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
+                                     C.c_void_p, C.POINTER(C.c_void_p)]
     L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
@@ -778,12 +784,28 @@ def blend_prepare(cfg, shapes_wh, homos, proj_method, identity_idx):
     return g, hinv, ranges
 
 
+GAIN_FIX = 2.0 ** 32                  # fixed-point scale of op_gain_overlap's colour sums
+GAIN_SIGMA_N, GAIN_SIGMA_G = 10.0 / 255.0, 0.1
+
+
+def _gains_array(gains, n):
+    if gains is None:
+        return None
+    g = np.ascontiguousarray(np.asarray(gains, np.float32))
+    if g.size == n:                    # one gain per image: all three channels
+        g = np.ascontiguousarray(np.repeat(g.reshape(n, 1), 3, axis=1))
+    if g.shape != (n, 3):
+        raise ValueError(f"gains must be ({n}, 3) or ({n},), got {g.shape}")
+    return g
+
+
 class BlendCall:
     """``ConnectedImages::blend()`` (stitcher_image.cc:116-155) with the op_blend_geom / op_blend_image arrays marshalled
-    once, like a C host holds them; every call is one op_blend.
+    once, like a C host holds them; every call is one op_blend -- or, with ``gains`` ((n, 3) or (n,) exposure gains), one
+    op_blend_gains.
     images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo."""
 
-    def __init__(self, ctx: Context, cfg, images, homos, proj_method, identity_idx):
+    def __init__(self, ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None):
         self.ctx = ctx
         n = self.n = len(images)
         arr_img, self._keep = _mk_images(images)
@@ -797,18 +819,72 @@ class BlendCall:
             for k in range(4):
                 arr[i].range[k] = ranges[i, k]
         self.ccfg = OpConfig.from_config(cfg)
+        self.gains = _gains_array(gains, n)
         self._fn = lib().op_blend
 
     def __call__(self) -> Canvas:
         h = C.c_void_p()
-        check(self._fn(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, C.byref(h)))
+        if self.gains is None:
+            check(self._fn(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, C.byref(h)))
+        else:
+            check(lib().op_blend_gains(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n,
+                                       self.gains.ctypes.data_as(C.c_void_p), C.byref(h)))
         return Canvas(self.ctx, h)
 
+    def overlap_sums(self, stride=1):
+        """op_gain_overlap over this call's canvas -> (count (P,) int64, sums (P, 6) int64: S_ab[3], S_ba[3] in units of
+        2^-32), P = n (n - 1) / 2, pair (a < b) at index pair_index(n, a, b)."""
+        npairs = self.n * (self.n - 1) // 2
+        count = np.zeros(max(npairs, 1), np.int64); sums = np.zeros((max(npairs, 1), 6), np.int64)
+        check(lib().op_gain_overlap(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(stride),
+                                    count.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
+        return count[:npairs], sums[:npairs]
 
-def blend(ctx: Context, cfg, images, homos, proj_method, identity_idx) -> Canvas:
+
+def blend(ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None) -> Canvas:
     """``ConnectedImages::blend()`` (stitcher_image.cc:116-155) on the device.
-    images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo."""
-    return BlendCall(ctx, cfg, images, homos, proj_method, identity_idx)()
+    images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo.
+    gains: optional (n, 3) or (n,) exposure gains (op_blend_gains); None = op_blend."""
+    return BlendCall(ctx, cfg, images, homos, proj_method, identity_idx, gains=gains)()
+
+
+def pair_index(n, a, b):
+    """index of the pair (a < b) in op_gain_overlap's arrays"""
+    return a * n - a * (a + 1) // 2 + (b - a - 1)
+
+
+def gain_overlap_sums(ctx: Context, cfg, images, homos, proj_method, identity_idx, stride=1):
+    """op_gain_overlap -> (count (P,) int64, sums (P, 6) int64 fixed point, 2^32 = 1.0)"""
+    return BlendCall(ctx, cfg, images, homos, proj_method, identity_idx).overlap_sums(stride)
+
+
+def gain_overlap(ctx: Context, cfg, images, homos, proj_method, identity_idx, stride=1):
+    """Overlap statistics of exposure compensation (op_gain_overlap) -> (count (P,) int64, means (P, 6) float64):
+    means[p] = (I_ab[3], I_ba[3]), the mean colour of image a and of image b over their common valid samples
+    (0 where count is 0); pair (a < b) at pair_index(n, a, b)."""
+    count, sums = gain_overlap_sums(ctx, cfg, images, homos, proj_method, identity_idx, stride)
+    den = GAIN_FIX * np.maximum(count, 1).astype(np.float64)
+    return count, np.where(count[:, None] > 0, sums.astype(np.float64) / den[:, None], 0.0)
+
+
+def gain_solve(n, count, sums, sigma_n=GAIN_SIGMA_N, sigma_g=GAIN_SIGMA_G, per_channel=True):
+    """op_gain_solve (host only): exposure gains (n, 3) float32 from op_gain_overlap's count / fixed-point sums."""
+    npairs = n * (n - 1) // 2
+    c = np.ascontiguousarray(np.asarray(count, np.int64).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(sums, np.int64).reshape(-1, 6))
+    if len(c) != npairs or len(s) != npairs:
+        raise ValueError(f"{n} images need {npairs} pairs, got {len(c)} counts and {len(s)} sums")
+    out = np.zeros((n, 3), np.float32)
+    check(lib().op_gain_solve(int(n), c.ctypes.data_as(C.c_void_p) if npairs else None, s.ctypes.data_as(C.c_void_p) if npairs else None,
+                              float(sigma_n), float(sigma_g), int(bool(per_channel)), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def gain_compensate(ctx: Context, cfg, images, homos, proj_method, identity_idx, stride=1, sigma_n=GAIN_SIGMA_N,
+                    sigma_g=GAIN_SIGMA_G, per_channel=True):
+    """op_gain_overlap + op_gain_solve: the exposure gains (n, 3) to pass to blend(..., gains=)"""
+    count, sums = gain_overlap_sums(ctx, cfg, images, homos, proj_method, identity_idx, stride)
+    return gain_solve(len(images), count, sums, sigma_n, sigma_g, per_channel)
 
 
 def cyl_warp_shape(cfg, w, h, h_factor, pts=None):

@@ -604,24 +604,17 @@ inline op_blend_geom hip_blend_prepare(const Bundle& b, std::vector<double>& hin
 // (config::MULTIBAND > 0 ? MultiBandBlender : LinearBlender).
 // crop = true additionally applies crop() (lib/imgproc.cc:200-235; main.cc:226-229 under config
 // CROP) on the device, so only the cropped pixels cross PCIe.
+// Exposure (gain) compensation -- an extension beyond the reference (Brown & Lowe, IJCV 2007, section 6; the C-ABI's
+// op_gain_overlap + op_gain_solve): the n x 3 gains that equalise the bundle's overlaps, from the samples the linear
+// blender takes on the canvas lattice of the given stride.  Pass them to hip_blend(b, crop, gains).
 template <typename Bundle>
-inline Mat32f hip_blend(const Bundle& b, bool crop = false) {
-	op_ctx* ctx = HipContext::get();
-	const op_config cfg = hip_config_snapshot();
+inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_geom& g) {
 	const int n = (int)b.component.size();
 	const Vec2D res = b.get_final_resolution();
-	op_blend_geom g;
 	g.proj_method = (int)b.proj_method;
 	g.proj_min[0] = b.proj_range.min.x; g.proj_min[1] = b.proj_range.min.y;
 	g.proj_max[0] = b.proj_range.max.x; g.proj_max[1] = b.proj_range.max.y;
 	g.resolution[0] = res.x; g.resolution[1] = res.y;
-#ifdef OPENPANO_WITH_REFERENCE
-	{	// the line ConnectedImages::blend prints (stitcher_image.cc:121-124); the reference's run_test.py scrapes it
-		const Vec2D size_d = b.proj_range.size() / res;
-		const Coor size(size_d.x, size_d.y);
-		print_debug("Final Image Size: (%d, %d)\n", size.x, size.y);
-	}
-#endif
 	std::vector<op_blend_image> ims(n);
 	for (int i = 0; i < n; ++i) {
 		auto& c = b.component[i];
@@ -631,8 +624,43 @@ inline Mat32f hip_blend(const Bundle& b, bool crop = false) {
 		for (int k = 0; k < 9; ++k) ims[i].homo_inv[k] = c.homo_inv[k];
 		ims[i].range[0] = c.range.min.x; ims[i].range[1] = c.range.min.y; ims[i].range[2] = c.range.max.x; ims[i].range[3] = c.range.max.y;
 	}
+	return ims;
+}
+template <typename Bundle>
+inline std::vector<float> hip_gain_compensate(const Bundle& b, int stride = 1, double sigma_n = 10.0 / 255.0, double sigma_g = 0.1,
+		bool per_channel = true) {
+	op_ctx* ctx = HipContext::get();
+	const op_config cfg = hip_config_snapshot();
+	const int n = (int)b.component.size();
+	op_blend_geom g;
+	const std::vector<op_blend_image> ims = hip_blend_images(b, g);
+	const size_t npairs = (size_t)n * (n - 1) / 2;
+	std::vector<int64_t> count(npairs + 1), sums(6 * npairs + 1);
+	std::vector<float> gains((size_t)3 * n);
+	PANO_HIP_CHECK(op_gain_overlap(ctx, &cfg, &g, ims.data(), n, stride, count.data(), sums.data()));
+	PANO_HIP_CHECK(op_gain_solve(n, count.data(), sums.data(), sigma_n, sigma_g, per_channel ? 1 : 0, gains.data()));
+	return gains;
+}
+
+// gains: empty = op_blend, else n x 3 exposure gains (op_blend_gains)
+template <typename Bundle>
+inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains) {
+	op_ctx* ctx = HipContext::get();
+	const op_config cfg = hip_config_snapshot();
+	const int n = (int)b.component.size();
+	op_blend_geom g;
+#ifdef OPENPANO_WITH_REFERENCE
+	{	// the line ConnectedImages::blend prints (stitcher_image.cc:121-124); the reference's run_test.py scrapes it
+		const Vec2D size_d = b.proj_range.size() / b.get_final_resolution();
+		const Coor size(size_d.x, size_d.y);
+		print_debug("Final Image Size: (%d, %d)\n", size.x, size.y);
+	}
+#endif
+	const std::vector<op_blend_image> ims = hip_blend_images(b, g);
+	if (!gains.empty() && gains.size() != (size_t)3 * n) { fprintf(stderr, "hip_blend: %zu gains for %d images\n", gains.size(), n); exit(1); }
 	op_canvas* cv = nullptr;
-	PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
+	if (gains.empty()) PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
+	else PANO_HIP_CHECK(op_blend_gains(ctx, &cfg, &g, ims.data(), n, gains.data(), &cv));
 	if (crop) {
 		op_canvas* cc = nullptr;
 		PANO_HIP_CHECK(op_canvas_crop(ctx, cv, &cc, nullptr, nullptr));
@@ -646,6 +674,9 @@ inline Mat32f hip_blend(const Bundle& b, bool crop = false) {
 	op_canvas_free(cv);
 	return out;
 }
+
+template <typename Bundle>
+inline Mat32f hip_blend(const Bundle& b, bool crop = false) { return hip_blend(b, crop, std::vector<float>()); }
 
 #ifndef OPENPANO_WITH_REFERENCE
 inline void ConnectedImages::prepare(bool set_inverse, bool set_range) {
@@ -773,7 +804,9 @@ class HipStitcher {
 			else build_linear_simple();
 			bundle.proj_method = config::ESTIMATE_CAMERA ? ConnectedImages::spherical : ConnectedImages::flat;
 			bundle.update_proj_range();
-			return bundle.blend();
+			if (!gain_compensation) { gains.clear(); return bundle.blend(); }
+			gains = hip_gain_compensate(bundle);                    // after the homographies are final
+			return hip_blend(bundle, false, gains);
 		}
 
 		std::vector<ImageRef> imgs;
@@ -783,6 +816,10 @@ class HipStitcher {
 		ConnectedImages bundle;
 		std::vector<Camera> cameras;
 		uint32_t base_seed;
+		// exposure (gain) compensation before the blend (hip_gain_compensate): an extension, off by default; `gains` holds
+		// the n x 3 gains the last build() used (empty when it used none)
+		bool gain_compensation = false;
+		std::vector<float> gains;
 
 		void calc_feature() {                                       // stitcherbase.cc:9-27
 			std::vector<const Mat32f*> ptrs;

@@ -11,6 +11,10 @@
 // configs 2-4): all pairs matched, homography RANSAC, host camera estimation + bundle adjustment
 // (pano_camera.hh), spherical blend; out.bin then carries n*13 f64 cameras (focal, aspect, ppx,
 // ppy, R) in place of the chain homographies, before the canvas.
+// "camera_build": the same branch through HipStitcher::build() itself (Stitcher st(mats); st.build()); out.bin then
+// holds only int32 H, W ; H*W*3 f32 [; n*3 f32 gains under --gain-compensation].
+// --gain-compensation (anywhere on the line): exposure compensation before the blend (HipStitcher::gain_compensation,
+// hip_gain_compensate: an extension beyond the reference); out.bin then ends with n*3 f32 gains after the canvas.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
@@ -70,7 +74,7 @@ static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::
 
 // Stitcher::build() under ESTIMATE_CAMERA (stitch/stitcher.cc:32-64), stage by stage so that every
 // intermediate can be written out
-static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered) {
+static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain) {
 	Stitcher st(mats, base_seed);
 	FILE* fo = fopen(out_path, "wb");
 	if (!fo) { perror(out_path); return 2; }
@@ -96,16 +100,45 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 	}
 	st.bundle.proj_method = ConnectedImages::spherical;
 	st.bundle.update_proj_range();
-	Mat32f pano = st.bundle.blend();
+	if (gain) st.gains = hip_gain_compensate(st.bundle);          // what HipStitcher::build() does under gain_compensation
+	Mat32f pano = gain ? hip_blend(st.bundle, false, st.gains) : st.bundle.blend();
 	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
+	if (gain) {
+		put(fo, st.gains.data(), st.gains.size());
+		for (int k = 0; k < n; ++k) fprintf(stderr, "gain %d: %g %g %g\n", k, st.gains[3 * k], st.gains[3 * k + 1], st.gains[3 * k + 2]);
+	}
 	fclose(fo);
 	return 0;
 }
 
+// Stitcher::build() as a client calls it, gain compensation per HipStitcher::gain_compensation
+static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain) {
+	Stitcher st(mats, base_seed);
+	st.gain_compensation = gain;
+	Mat32f pano = st.build();
+	FILE* fo = fopen(out_path, "wb");
+	if (!fo) { perror(out_path); return 2; }
+	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
+	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
+	put(fo, st.gains.data(), st.gains.size());
+	fclose(fo);
+	fprintf(stderr, "Final Image Size: (%d, %d), %zu gains\n", pano.cols(), pano.rows(), st.gains.size());
+	return 0;
+}
+
 int main(int argc, char** argv) {
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed]\n", argv[0]); return 2; }
+	bool gain = false;
+	{	// --gain-compensation may stand anywhere; the positional arguments keep their places
+		int m = 1;
+		for (int k = 1; k < argc; ++k) {
+			if (std::string(argv[k]) == "--gain-compensation") gain = true;
+			else argv[m++] = argv[k];
+		}
+		argc = m;
+	}
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation]\n", argv[0]); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
@@ -119,10 +152,11 @@ int main(int argc, char** argv) {
 	}
 	fclose(fi);
 	const std::string mode = argc > 4 ? argv[4] : "";
-	const bool camera_mode = mode == "camera" || mode == "camera_ordered";
+	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
-	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered");
+	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain);
+	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain);
 
 	// ---- StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27)
 	std::vector<ImageRef> imgs;
@@ -187,10 +221,12 @@ int main(int argc, char** argv) {
 		}
 		bundle.calc_inverse_homo();
 		bundle.update_proj_range();
-		Mat32f pano = bundle.blend();
+		const std::vector<float> gains = gain ? hip_gain_compensate(bundle) : std::vector<float>();
+		Mat32f pano = hip_blend(bundle, false, gains);
 		put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 		put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 		for (auto& t : to_mid) put(fo, t.data, 9);
+		put(fo, gains.data(), gains.size());
 		fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
 	} else {
 		put1<int32_t>(fo, 0); put1<int32_t>(fo, 0);
