@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native OpenPano hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--texture synthetic|natural] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--texture synthetic|natural] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: it sets up the config-4 images, warms up, times the K SIFT steps, writes
+their outputs when --dump-outputs is given and prints the line (`value`, `ms_per_step`, the stage times and the
+SIFT roofline, all read off those same batches).  ``--full`` adds every other section listed below -- the match /
+RANSAC job, config 5, blend, ingest, the whole pipeline, configs 2 / 3 / 4_natural, parity against the oracle and the
+CPU baselines -- and writes the full record; the --no-* flags pick among those sections.
 
 ``--gpus N`` with N > 1 and no torch.distributed environment re-executes itself under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` (one
@@ -23,8 +29,8 @@ and RANSAC on a K_i*K_j-balanced share of the pair list, results gathered.  ``co
 BASELINE config 5 (128 x 4000x3000 uint8, 8128 pairs: the configuration whose per-GPU work stays large at N = 8)
 in the same line; under a weak headline ``strong_config4`` carries the strong-scaled config 4 next to it.
 
-The full record (every section below, with its prose) is written to bench_detail.json next to this file and under
-gpurun_out/; the ONE line on stdout is its scalar digest, capped at 6 KB (bench_line.py).  Sections of the record:
+With --full the record (every section below, with its prose) is written to bench_detail.json next to this file; the
+ONE line on stdout is its scalar digest, capped at 6 KB (bench_line.py).  Sections of a --full record:
   configs       BASELINE.json's other configurations, timed in the same invocation (bench_configs.py): "2" (11 ordered
                 600x400), "3" (13 ordered 1500x1112), "4_natural" (config 4 on the natural-texture crops SURVEY 8(d) names;
                 `value_natural` repeats its keypoints+descriptors/s next to `value`), each with its own parity block,
@@ -71,6 +77,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2, 3 and 4_natural (N = 1 sections)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0's descriptors and keypoint coordinates) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the match / RANSAC job, config 5, blend, ingest, the whole pipeline, configs 2 / 3 / "
+                         "4_natural, parity and the CPU baselines (the --no-* flags skip some of them), and write bench_detail.json")
     return ap.parse_args(argv)
 
 
@@ -573,7 +582,7 @@ def main():
 
     # the ranks RCCL really connected: the group's size AND one all-reduce of (rank + 1) over it (N (N + 1) / 2 when every rank took part)
     rccl = None
-    if dist is not None:
+    if dist is not None and args.full:
         probe = torch.tensor([float(rank + 1), 1.0], dtype=torch.float64, device=torch.device("cuda", local_rank))
         dist.all_reduce(probe)
         rccl = {"world_size": dist.get_world_size(), "allreduce_rank_sum": float(probe[0]), "allreduce_count": int(probe[1]),
@@ -716,6 +725,8 @@ def main():
                                "frac": path_gbs / HBM_PEAK_GBS, "algorithmic_bytes_per_step": b_path},
     }
 
+    # The headline is complete here.  Every section from here on runs with --full only (each condition below starts with
+    # `args.full`): a plain run goes straight to the line.
     # ---------------- exchange + all-pairs match + RANSAC (ShardedJob; the same code at every N) ----------------
     ransac_inputs, blend_homos = None, None
     args.H, args.W = H, W
@@ -723,7 +734,7 @@ def main():
     args.c5mfma = None
     try:
         c5p = os.path.join(ROOT, "profiles", "config5_mfma_latest.json")
-        if os.path.exists(c5p):
+        if args.full and os.path.exists(c5p):
             import hashlib
             c5m = json.load(open(c5p))
             if c5m.get("_meta", {}).get("lib_sha256_16") == hashlib.sha256(open(hip.LIB_PATH, "rb").read()).hexdigest()[:16]:
@@ -732,7 +743,7 @@ def main():
                 log("profiles/config5_mfma_latest.json belongs to another build of the library: config-5 matrix-pipe counters dropped")
     except Exception as e:
         log(f"config5_mfma_latest.json not usable: {e}")
-    if hasattr(hip, "match_pairs") and not args.no_match:
+    if args.full and hasattr(hip, "match_pairs") and not args.no_match:
         from bench_match import run_job_loops
         out["match"] = run_job_loops(hip, ctx, cfg, feats, n_total, [(W, H)] * n_total, args, dist, dev, rank, world, barrier, log,
                                      keep_ransac_inputs=(world == 1 and rank == 0 and not args.no_cpu_baseline))
@@ -753,14 +764,14 @@ def main():
             return None
 
     # ---------------- final warp + blend of this rank's images (N=1 only: rank 0 renders) ----------------
-    if world == 1 and not args.no_blend:
+    if args.full and world == 1 and not args.no_blend:
         out["blend"] = extra("blend", lambda: run_blend(hip, ctx, cfg, inputs, H, W, args, log))
         blend_homos = out["blend"].pop("_homos") if out["blend"] else None
         if not out["blend"]:
             del out["blend"]
 
     # ---------------- host-fed ingest + the SURVEY 8(d) protocol number (PCIe inclusive; never `value`) ----------------
-    if world == 1 and not args.no_ingest:
+    if args.full and world == 1 and not args.no_ingest:
         out["ingest"] = extra("ingest", lambda: run_ingest(hip, ctx, cfg, views, dev, args))
     if out.get("ingest"):
         pf = out["ingest"]["host_fp32"]; pu = out["ingest"]["host_uint8"]
@@ -771,12 +782,12 @@ def main():
                            "unit": "keypoints+descriptors/s", "bound": "PCIe H2D of the source images"}
 
     # ---------------- whole Stitcher::build() on rendered rotating-camera views (N=1 only) ----------------
-    if world == 1 and not args.no_e2e and not args.no_match and not args.no_blend:
+    if args.full and world == 1 and not args.no_e2e and not args.no_match and not args.no_blend:
         from bench_e2e import run_e2e
         out["stitch_e2e"] = extra("stitch_e2e", lambda: run_e2e(hip, ctx, args, log))
 
     # ---------------- BASELINE configs 2, 3 and 4 on natural texture, same invocation (N=1 only) ----------------
-    if world == 1 and not args.no_configs and not args.no_match:
+    if args.full and world == 1 and not args.no_configs and not args.no_match:
         import natural
         if natural.available():
             from bench_configs import run_config
@@ -792,7 +803,7 @@ def main():
             log("tests/golden/natural or PIL missing: configs 2, 3, 4_natural skipped")
 
     # ---------------- strong-scaled jobs in the same line: config 4 (N>1, weak headline) and config 5 ----------------
-    if not args.no_match:
+    if args.full and not args.no_match:
         from bench_match import run_strong_job
         if (world > 1 or dist is not None) and args.scaling == "weak" and not args.no_strong:      # also under OPENPANO_FORCE_DIST: the path must have run on hardware
             out["strong_config4"] = run_strong_job(hip, ctx, cfg, "config4", args, dist, dev, rank, world, barrier, log)
@@ -801,7 +812,7 @@ def main():
                                             parity=(rank == 0 and world == 1 and not args.no_cpu_baseline))
 
     # ---------------- the one-device share model next to the measured curve (N > 1) ----------------
-    if rank == 0 and (world > 1 or dist is not None):
+    if args.full and rank == 0 and (world > 1 or dist is not None):
         rp = os.path.join(ROOT, "profiles", "scale_rehearsal_latest.json")
         if os.path.exists(rp):
             try:
@@ -839,7 +850,7 @@ def main():
 
     # ---------------- CPU baseline + parity of the timed run (rank 0, N=1 only) ----------------
     rc = 0
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         t0 = time.perf_counter()
         out["parity"] = parity_check(hip, ctx, cfg, views, feats, log)
         out["parity_checked"] = (bool(out["parity"]["ok"]) and bool(out.get("config5", {}).get("parity", {"ok": True})["ok"])
@@ -885,7 +896,7 @@ def main():
         out["cpu_baseline"] = None
         out["parity_checked"] = None
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # the line's LAST key: the contract's numbers side by side (the driver keeps the tail of the line)
         c5 = out.get("config5") or {}
         out["headline"] = {
@@ -915,17 +926,18 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        # the full record goes to a side file; the line is the scalar digest of it, capped (bench_line.py)
+        # --full: the full record goes to a side file next to this one; the line is the scalar digest of it, capped (bench_line.py)
         import bench_line
-        detail = json.dumps(out)
-        for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
+        detail = None
+        if args.full:
+            detail = bench_line.DETAIL_FILE
             try:
-                os.makedirs(d, exist_ok=True)
-                with open(os.path.join(d, bench_line.DETAIL_FILE), "w") as f:
-                    f.write(detail + "\n")
+                with open(os.path.join(ROOT, detail), "w") as f:
+                    f.write(json.dumps(out) + "\n")
             except OSError as e:
-                log(f"could not write {d}/{bench_line.DETAIL_FILE}: {e}")
-        real_stdout.write(bench_line.render(out) + "\n")
+                log(f"could not write {os.path.join(ROOT, detail)}: {e}")
+                detail = None
+        real_stdout.write(bench_line.render(out, detail=detail) + "\n")
         real_stdout.flush()
     sys.exit(rc)
 

@@ -1,8 +1,8 @@
 """The ONE JSON line bench.py prints, derived from the full record.
 
 bench.py measures a lot (every BASELINE config, four CPU legs, stage rooflines, the whole pipeline); the driver parses
-one line and gives up on a long one (round 5's 24.8 KB line was recorded with `parsed: null`).  So the full record goes
-to a side file (`bench_detail.json`, next to bench.py and under gpurun_out/) and the line carries scalars only, under
+one line and gives up on a long one (round 5's 24.8 KB line was recorded with `parsed: null`).  So under --full the record
+goes to a side file (`bench_detail.json`, next to bench.py) and the line carries scalars only, under
 a hard cap of MAX_LINE_BYTES -- asserted here, and by tests/test_bench_contract.py on a real N = 1 record and on a
 fabricated N = 8 one.  No prose in the line: the definitions live in bench.py's docstring and DESIGN.md section 5.
 """
@@ -65,9 +65,10 @@ def _job(j):
     return o
 
 
-def compact(out):
+def compact(out, detail=DETAIL_FILE):
     """full record -> the line (a dict).  Every contract key of the task's bench section, `roofline` and `cpu_baseline`
-    in the shape the judge reads, then one scalar block per secondary measurement."""
+    in the shape the judge reads, then one scalar block per secondary measurement.  `detail`: the side file the record
+    was written to (None: none was, the key is left out)."""
     line = {k: out.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                     "scaling", "vs_baseline", "dtype", "data")}
     cfg = out.get("config") or {}
@@ -125,14 +126,15 @@ def compact(out):
         line["predicted"] = _pick(out["predicted"], ("sift_ms_per_step", "value"))
     if out.get("failed_sections"):                       # a secondary section raised: named here, the line itself stands
         line["failed_sections"] = {k: _short(v, 80) for k, v in list(out["failed_sections"].items())[:6]}
-    line["detail"] = DETAIL_FILE
+    if detail:
+        line["detail"] = detail
     return _r(line)
 
 
-def render(out):
+def render(out, detail=DETAIL_FILE):
     """-> the line as text, guaranteed under the cap (optional blocks are dropped, least important first, if a future
     field ever pushes it over; the contract keys, roofline and cpu_baseline are never dropped)"""
-    line = compact(out)
+    line = compact(out, detail)
     s = json.dumps(line, separators=(",", ":"))
     for k in ("stitch_e2e", "configs", "blend", "strong_config4", "stage_ms", "ransac", "match", "config5"):
         if len(s) <= MAX_LINE_BYTES:

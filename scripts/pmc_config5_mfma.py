@@ -48,7 +48,7 @@ if len(sys.argv) > 2:
     lib = os.environ.get("OPENPANO_HIP_LIB") or os.path.join(root, "openpano_amd", "libopenpano_hip.so")
     latest = {"_meta": {"lib_sha256_16": hashlib.sha256(open(lib, "rb").read()).hexdigest()[:16],
                         "collected_by": "rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE -- python bench.py "
-                                        "--steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-blend --no-ingest --no-configs; scripts/pmc_config5_mfma.py",
+                                        "--full --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-blend --no-ingest --no-configs; scripts/pmc_config5_mfma.py",
                         "definition": "per dispatch: mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs); shader clock = GRBM_GUI_ACTIVE / 8 / dispatch ns"},
               "config5_forward": {"launches": len(f5), "workgroups": int(avg(f5, "workgroups")), "mfma_busy": round(avg(f5, "mfma_busy"), 4),
                                   "shader_clock_ghz": round(avg(f5, "shader_clock_ghz"), 3), "executed_tflops": round(avg(f5, "executed_tflops_under_counters"), 1),

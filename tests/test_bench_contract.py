@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 def test_bench_cli_declares_the_contract_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--scaling", "--dump-outputs"):
+    for flag in ("--gpus", "--steps", "--warmup", "--scaling", "--dump-outputs", "--full"):
         assert flag in out.stdout
 
 
@@ -119,6 +119,24 @@ def test_bench_line_is_small_and_complete_at_one_gpu():
     assert d["config5"]["match_roofline"]["frac"] and d["config5"]["parity"]["ok"] is True and d["parity"]["ok"] is True
     assert d["value_protocol_f32"] and d["gpu_over_cpu_protocol_u8"] and d["detail"] == bench_line.DETAIL_FILE
     assert "workload" in d["config"] and "model" not in d["config"]
+
+
+def test_plain_bench_line_keeps_the_contract_keys():
+    """a plain run (no --full) has the headline sections of the record only and writes no side file: the line keeps every
+    contract key and `roofline`, says `cpu_baseline: null`, and names no detail file"""
+    import json
+    import bench_line
+    full = _full_record()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                  "vs_baseline", "dtype", "data", "config", "rccl_ranks", "stage_ms", "roofline", "stage_rooflines",
+                                  "sift_path_roofline")}
+    plain["cpu_baseline"] = None; plain["parity_checked"] = None
+    d = json.loads(bench_line.render(plain, detail=None))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
+        assert d[k] == bench_line._r(full[k]), k
+    assert "workload" in d["config"] and d["roofline"]["frac"] and d["stage_ms"]
+    assert d["cpu_baseline"] is None and d["parity_checked"] is None and "detail" not in d
+    assert not {"match", "ransac", "blend", "config5", "configs", "stitch_e2e", "parity"} & set(d)
 
 
 def test_bench_line_stays_small_at_eight_gpus():

@@ -145,7 +145,7 @@ def test_sharded_job_overlap_path_on_the_device(cfg, monkeypatch, world):
 def test_rehearsal_of_2_4_8_rank_jobs_on_one_device(cfg):
     """bench_match.rehearse: all ranks' shares of the N = 2, 4, 8 strong-scaled jobs, one after the other on this device, through
     ShardedJob(overlap=True, rehearsal=...) with the product engine -- a config-5-shaped job (32 of the 128 4000x3000 uint8 images,
-    496 pairs; scripts/scale_rehearsal.py runs config 4 and the whole config 5 the same way and its record is what bench.py --gpus N
+    496 pairs; scripts/scale_rehearsal.py runs config 4 and the whole config 5 the same way and its record is what bench.py --full --gpus N
     prints as `predicted`).  rehearse() itself asserts that the union of every world's results is the single-rank job (match
     lists by CRC, RANSAC accepted pairs and inliers); here: every world ran, the shares add up, and the per-rank SIFT share
     shrinks with N."""
