@@ -373,6 +373,44 @@ int op_gain_solve(int n, const int64_t* count, const int64_t* sums, double sigma
 int op_blend_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n,
 		const float* gains, op_canvas** out);
 
+/* ---- BLOCK GAIN COMPENSATION (ABI 10) -- the gains above, one per block of a bx x by grid on every image instead of one
+ * per image (as OpenCV's BlocksGainCompensator): it also evens out brightness that varies INSIDE a view (vignetting, sky
+ * gradients, metering).  Opt-in; bx = by = 1 reduces exactly to the per-image entry points.
+ *
+ * Blocks.  Image k (op_blend_image h x w -- the ImageRef size, also after a cylinder pre-warp) is split into bx x by blocks,
+ * bx, by in [1, 16], B = bx * by; unit (k, q), q = v * bx + u, is block (u, v) of image k.  A sample at image coordinates
+ * (r, c) -- the floats the linear blender passes to interpolate() -- lies in block, in fp32 exactly,
+ *   u = clamp((int)floorf(c * (float)bx / (float)w), 0, bx - 1),   v = clamp((int)floorf(r * (float)by / (float)h), 0, by - 1).
+ *
+ * op_gain_block_overlap: op_gain_overlap's statistics (same lattice, validity rules, LAZY_READ branches, fixed point)
+ * split by block pair: pair p (a < b, index as above) and blocks (qa, qb) of its samples at entry e = p * B^2 + qa * B + qb:
+ * count[e], sums[6e .. 6e + 5] = S_ab[3], S_ba[3].  count: P * B^2, sums: P * B^2 * 6 (P = n (n - 1) / 2; both may be NULL
+ * when n == 1).  At most 2^22 entries P * B^2 (OP_ERR_UNSUPPORTED beyond; 128 images at 4 x 4 use 2.1 M).
+ * op_gain_block_solve (HOST ONLY): the unit gains minimising
+ *   e = 1/2 sum_{unit pairs (a,qa),(b,qb), a != b} N [ (g_{a,qa} I - g_{b,qb} I')^2 / sigma_n^2 + (1 - g_{a,qa})^2 / sigma_g^2 ]
+ *     + 1/2 sum_k sum_{4-neighbour blocks q ~ q'} lambda_k (g_{k,q} - g_{k,q'})^2 / sigma_s^2,     lambda_k = M_k / B,
+ * both sums over ordered pairs (every edge counts twice, like every unit pair), N / I / I' the count and means of the
+ * entry, M_k the overlap count of image k over all its pairs (the smoothness term in the data term's sample units).
+ * Every unit of an image with any overlap is unknown -- a block that overlaps nothing takes its gain from its neighbours
+ * through the smoothness term; an image without overlap gets 1.  Usual sigma_s = 0.1.  per_channel as op_gain_solve.
+ * gains: n * by * bx * 3, gains[((k * by + v) * bx + u) * 3 + c].  fp64 dense Cholesky, fixed order; with bx = by = 1 the
+ * floats of op_gain_solve.  At most n * B = 4096 units (OP_ERR_UNSUPPORTED beyond).
+ * op_blend_block_gains: op_blend with every valid sample (linear blender; multiband level 0) of image k at (r, c) scaled
+ * by its block-centre gains interpolated bilinearly in fp32, clamped at the border:
+ *   fx = c * (float)bx / (float)w - 0.5f, u0 = clamp(floorf(fx), 0, bx - 1), u1 = min(u0 + 1, bx - 1),
+ *   tx = clamp(fx - u0, 0, 1) (the same for y), lerp(a, b, t) = a + t * (b - a),
+ *   g = lerp(lerp(G[v0][u0], G[v0][u1], tx), lerp(G[v1][u0], G[v1][u1], tx), ty),
+ * then col[c] = min(col[c] * g, 1), a channel whose g is exactly 1 left as it is.  A uniform map G_k gives
+ * op_blend_gains(G)'s canvas bit for bit; NULL = op_blend.  gains finite and > 0.
+ * Bad arguments (NULLs, n < 1, stride < 1, bx / by outside [1, 16], non-positive or non-finite sigmas / gains) return
+ * OP_ERR_INVALID.  Threading and ownership as the per-image entry points. */
+int op_gain_block_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
+		int bx, int by, int64_t* count, int64_t* sums);
+int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, double sigma_s,
+		int per_channel, float* gains);
+int op_blend_block_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int bx, int by,
+		const float* gains, op_canvas** out);
+
 /* CYLINDER mode pre-warp -- replaces CylinderWarper::warp (stitch/warp.hh:47-55, warp.cc:13-75).
  * op_cyl_warp_shape is the host part (projector, output shape, offset and the keypoints, which
  * are centred coordinates updated in place: warp.cc:46-67); op_cyl_warp renders the pixels. */

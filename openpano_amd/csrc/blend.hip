@@ -158,11 +158,51 @@ __device__ __forceinline__ void apply_gain(const float* __restrict__ g, float (&
 	for (int ch = 0; ch < 3; ++ch) { const float gc = g[ch]; if (gc != 1.f) col[ch] = fminf(col[ch] * gc, 1.f); }
 }
 
-// ---- LinearBlender::run (blender.cc:24-96): thread per canvas pixel, images in index order.  GAIN: gains (n x 3)
-// scale every sample (op_blend_gains); without it the kernel is op_blend's ----
-template <bool GAIN>
+// Block gains (op_gain_block_overlap / op_blend_block_gains): image k -- ImageRef size w x h, the bounds linear_sample tests
+// against -- is split into bx x by blocks; block (u, v) is unit q = v * bx + u.  A sample at image coordinates (r, c) -- the
+// floats linear_sample returns and interpolate() reads -- lies in the block below.  This exact fp32 expression is part of the
+// contract (include/openpano_hip.h); the CPU restatements copy it.
+constexpr int GAIN_NONE = 0, GAIN_IMAGE = 1, GAIN_BLOCK = 2;   // gain modes of the blend kernels
+constexpr int GAIN_MAX_BLOCKS = 16;                           // bx, by in [1, 16]
+__device__ __forceinline__ int gain_block_of(float r, float c, int w, int h, int bx, int by) {
+	int u = (int)floorf(c * (float)bx / (float)w), v = (int)floorf(r * (float)by / (float)h);
+	u = u < 0 ? 0 : (u > bx - 1 ? bx - 1 : u);
+	v = v < 0 ? 0 : (v > by - 1 ? by - 1 : v);
+	return v * bx + u;
+}
+// one axis of the bilinear interpolation between block centres, clamped at the border: the cells i0, i1 and the weight t
+__device__ __forceinline__ void gain_block_axis(float x, int nb, int dim, int& i0, int& i1, float& t) {
+	const float f = x * (float)nb / (float)dim - 0.5f;
+	int a = (int)floorf(f);
+	a = a < 0 ? 0 : (a > nb - 1 ? nb - 1 : a);
+	i0 = a; i1 = a + 1 < nb ? a + 1 : nb - 1;
+	float tt = f - (float)a;
+	t = tt < 0.f ? 0.f : (tt > 1.f ? 1.f : tt);
+}
+// The gain at (r, c) of an image whose by x bx x 3 block gains start at G, interpolated bilinearly between block centres as
+// lerp(a, b, t) = a + t (b - a): a uniform map gives exactly its value (b - a = 0), so it reproduces apply_gain bit for bit.
+// Then applied per channel as apply_gain does.
+__device__ __forceinline__ void apply_block_gain(const float* __restrict__ G, int bx, int by, int w, int h, float r, float c, float (&col)[3]) {
+	int u0, u1, v0, v1; float tx, ty;
+	gain_block_axis(c, bx, w, u0, u1, tx);
+	gain_block_axis(r, by, h, v0, v1, ty);
+	const float* g00 = G + (v0 * bx + u0) * 3; const float* g01 = G + (v0 * bx + u1) * 3;
+	const float* g10 = G + (v1 * bx + u0) * 3; const float* g11 = G + (v1 * bx + u1) * 3;
+#pragma unroll
+	for (int ch = 0; ch < 3; ++ch) {
+		const float top = g00[ch] + tx * (g01[ch] - g00[ch]);
+		const float bot = g10[ch] + tx * (g11[ch] - g10[ch]);
+		const float gc = top + ty * (bot - top);
+		if (gc != 1.f) col[ch] = fminf(col[ch] * gc, 1.f);
+	}
+}
+
+// ---- LinearBlender::run (blender.cc:24-96): thread per canvas pixel, images in index order.  GM: GAIN_IMAGE -- gains
+// (n x 3) scale every sample (op_blend_gains); GAIN_BLOCK -- gains (n x gby x gbx x 3) are interpolated at the sample
+// (op_blend_block_gains); GAIN_NONE -- the kernel is op_blend's.  gbx / gby are read by GAIN_BLOCK only ----
+template <int GM>
 __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
-		float* __restrict__ out, int H, int W, int ordered_input, int lazy, const float* __restrict__ gains) {
+		float* __restrict__ out, int H, int W, int ordered_input, int lazy, const float* __restrict__ gains, int gbx, int gby) {
 	__shared__ unsigned long long s_cover[COVER_WORDS];
 	const int j = blockIdx.x * 64 + (threadIdx.x & 63);
 	const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -177,7 +217,8 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 			const BlendImg& im = imgs[k];
 			float r, c, col[3];
 			if (!linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col)) return;
-			if (GAIN) apply_gain(gains + 3 * (long long)k, col);
+			if (GM == GAIN_IMAGE) apply_gain(gains + 3 * (long long)k, col);
+			if (GM == GAIN_BLOCK) apply_block_gain(gains + 3 * (long long)k * gbx * gby, gbx, gby, im.w, im.h, r, c, col);
 			float w = (float)(0.5 - fabs((double)(c / (float)im.w) - 0.5));
 			if (!ordered_input) w = (float)((double)w * (0.5 - fabs((double)(r / (float)im.h) - 0.5)));
 			s0 += col[0] * w; s1 += col[1] * w; s2 += col[2] * w;
@@ -301,6 +342,99 @@ __global__ void __launch_bounds__(256) k_gain_overlap(BlendGeom g, BlendTrig tri
 	}
 }
 
+// ---- block statistics for op_gain_block_overlap: k_gain_overlap with every slot also carrying its sample's block
+// (gain_block_of), and the statistics of pair p split by block pair, entry e = p * B^2 + qa * B + qb (B = bx * by).  The
+// lanes of a wavefront -- a row of 64 lattice points -- can fall into different block pairs where a block border crosses
+// the row, so a pair is reduced per distinct key: the key of the first lane left (readlane), the butterfly sums of the
+// lanes sharing it, one set of 64-bit atomics, those lanes dropped, again.  Most wavefronts hold one key: one round.
+constexpr long long GAIN_BLOCK_MAX_ENTRIES = 1ll << 22;    // P * B^2 (include/openpano_hip.h)
+constexpr long long GAIN_BLOCK_MAX_UNKNOWNS = 4096;        // n * B, op_gain_block_solve's dense Cholesky
+__device__ __forceinline__ void gain_block_pair(int a, int b, int n, int nblk, bool va, int qa, const float (&x)[3], bool vb, int qb,
+		const float (&y)[3], unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+	const bool both = va && vb;
+	unsigned long long bal = __ballot(both);
+	if (!bal) return;                                   // wave-uniform
+	long long v[6];
+#pragma unroll
+	for (int ch = 0; ch < 3; ++ch) {
+		v[ch] = both ? llrint((double)x[ch] * GAIN_FIX) : 0;
+		v[3 + ch] = both ? llrint((double)y[ch] * GAIN_FIX) : 0;
+	}
+	const int key = qa * nblk + qb;
+	const long long base = ((long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1)) * nblk * nblk;
+	while (bal) {                                       // wave-uniform: one round per distinct block pair
+		const int k0 = __builtin_amdgcn_readlane(key, __builtin_ctzll(bal));
+		const bool mine = both && key == k0;
+		const unsigned long long mb = __ballot(mine);
+		long long s[6];
+#pragma unroll
+		for (int q = 0; q < 6; ++q) s[q] = wave_sum(mine ? v[q] : 0);
+		if ((threadIdx.x & 63) == 0) {
+			const long long e = base + k0;
+			atomicAdd(count + e, (unsigned long long)__popcll(mb));
+#pragma unroll
+			for (int q = 0; q < 6; ++q) atomicAdd(sums + 6 * e + q, (unsigned long long)s[q]);
+		}
+		bal &= ~mb;
+	}
+}
+__global__ void __launch_bounds__(256) k_gain_block_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
+		int H, int W, int stride, int lazy, int bx, int by, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+	extern __shared__ unsigned long long s_gcover[];
+	const int words = (n + 63) >> 6;
+	const int nblk = bx * by;
+	const int i = (blockIdx.y * 4 + (threadIdx.x >> 6)) * stride;
+	const int j = (blockIdx.x * 64 + (threadIdx.x & 63)) * stride;
+	const bool live = i < H && j < W;
+	{	// tile_cover over all n images at once (as k_gain_overlap)
+		const int i0 = blockIdx.y * 4 * stride, j0 = blockIdx.x * 64 * stride, excl = lazy ? 1 : 0;
+		for (int k = (int)threadIdx.x; k < words * 64; k += 256) {
+			bool hit = false;
+			if (k < n) {
+				const BlendImg& im = imgs[k];
+				hit = im.x0 <= j0 + 63 * stride && im.x1 - excl >= j0 && im.y0 <= i0 + 3 * stride && im.y1 - excl >= i0;
+			}
+			const unsigned long long b = __ballot(hit);
+			if ((threadIdx.x & 63) == 0) s_gcover[k >> 6] = b;
+		}
+		__syncthreads();
+	}
+	double hx, hy, hz;
+	proj2homo(g, trig, i, j, hx, hy, hz);
+	auto sample = [&](int k, float (&col)[3], int& q) -> bool {
+		float r, c;
+		q = 0;
+		const BlendImg& im = imgs[k];
+		if (!(live && linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col))) return false;
+		q = gain_block_of(r, c, im.w, im.h, bx, by);
+		return true;
+	};
+	int a0 = next_cover(s_gcover, words, 0);
+	while (a0 < n) {
+		int ka[GAIN_CH], qa[GAIN_CH]; bool va[GAIN_CH]; float ca[GAIN_CH][3];
+		int k = a0;
+#pragma unroll
+		for (int s = 0; s < GAIN_CH; ++s) {
+			ka[s] = k;
+			va[s] = false; qa[s] = 0;
+			if (k < n) { va[s] = sample(k, ca[s], qa[s]); k = next_cover(s_gcover, words, k + 1); }
+		}
+#pragma unroll
+		for (int s = 0; s < GAIN_CH; ++s)
+#pragma unroll
+			for (int t = s + 1; t < GAIN_CH; ++t)
+				if (ka[t] < n) gain_block_pair(ka[s], ka[t], n, nblk, va[s], qa[s], ca[s], va[t], qa[t], ca[t], count, sums);
+		const int a1 = k;
+		for (int b = a1; b < n; b = next_cover(s_gcover, words, b + 1)) {
+			float cb[3]; int qb;
+			const bool vb = sample(b, cb, qb);
+#pragma unroll
+			for (int s = 0; s < GAIN_CH; ++s) gain_block_pair(ka[s], b, n, nblk, va[s], qa[s], ca[s], vb, qb, cb, count, sums);
+		}
+		a0 = a1;
+	}
+}
+
 // ---- create_first_level + update_weight_map (multiband.cc:19-56,125-143) in ONE pass, thread per canvas pixel:
 // proj2homo once per pixel (it does not depend on the image), then every image whose ROI covers the pixel in index
 // order: its level-0 WeightedPixel is written with weight 0 while the winner of the winner-takes-all map -- the first
@@ -308,11 +442,12 @@ __global__ void __launch_bounds__(256) k_gain_overlap(BlendGeom g, BlendTrig tri
 // the winner's weight is then set to 1 with one 4-byte store.  The ROI planes are written once and never read back
 // (the two-kernel form re-read every weight and rewrote it: 0.49 GB of the 1.33 GB the two kernels moved), and the
 // target canvas / its "seen" mask are initialised here too (fill(target, Color::NO), multiband.cc:60-61).
-// GAIN: the level-0 colours are the gained samples (op_blend_gains); the weights do not depend on colour.
-template <bool GAIN>
+// GM (as k_blend_linear's): the level-0 colours are the gained samples (op_blend_gains, op_blend_block_gains -- the block
+// gain interpolated at the floats interpolate() reads); the weights do not depend on colour.
+template <int GM>
 __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		float4* __restrict__ cur, unsigned char* __restrict__ mask, float* __restrict__ out, unsigned char* __restrict__ tmask, int H, int W,
-		const float* __restrict__ gains) {
+		const float* __restrict__ gains, int gbx, int gby) {
 	const int j = blockIdx.x * 64 + (threadIdx.x & 63);
 	const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
 	// The target is as large as the largest bottom-right ROI coordinate (blender.cc:21) while ROIs are inclusive
@@ -337,7 +472,8 @@ __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig t
 			float col[3];
 			bool ok = interpolate(im.data, im.mh, im.mw, (float)oy, (float)ox, col);
 			if (ok) { float mn = fminf(col[0], fminf(col[1], col[2])); if (mn < 0) ok = false; }
-			if (GAIN && ok) apply_gain(gains + 3 * (long long)k, col);
+			if (GM == GAIN_IMAGE && ok) apply_gain(gains + 3 * (long long)k, col);
+			if (GM == GAIN_BLOCK && ok) apply_block_gain(gains + 3 * (long long)k * gbx * gby, gbx, gby, im.w, im.h, (float)oy, (float)ox, col);
 			float4 px = make_float4(0.f, 0.f, 0.f, 0.f);
 			if (ok) {
 				const double x = ox / (double)im.w - 0.5, y = oy / (double)im.h - 0.5;
@@ -987,9 +1123,10 @@ int check_blend_args(const char* who, const op_blend_geom* g) {
 	return OP_OK;
 }
 
-// op_blend (gains == NULL) and op_blend_gains (gains: n x 3 on the host)
+// op_blend (gains == NULL), op_blend_gains (gbx == 0, gains: n x 3 on the host) and op_blend_block_gains (gbx, gby >= 1,
+// gains: n x gby x gbx x 3 on the host)
 int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
-		const char* who, op_canvas** out) {
+		int gbx, int gby, const char* who, op_canvas** out) {
 	int rc = check_blend_args(who, g);
 	if (rc != OP_OK) return rc;
 	HIPCHK(hipSetDevice(ctx->device));
@@ -1005,9 +1142,11 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	rc = upload_images(ctx, who, g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
 	if (rc != OP_OK) return rc;
 	float* d_gains = nullptr;
-	if (gains) {
-		HIPCHK(pool_alloc((void**)&d_gains, sizeof(float) * 3 * (size_t)n)); fr.v.push_back(d_gains);
-		HIPCHK(hipMemcpyAsync(d_gains, gains, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+	const int gm = !gains ? GAIN_NONE : (gbx > 0 ? GAIN_BLOCK : GAIN_IMAGE);
+	if (gains) {                 // the whole table, once per call
+		const size_t ng = 3 * (size_t)n * (gm == GAIN_BLOCK ? (size_t)gbx * gby : 1);
+		HIPCHK(pool_alloc((void**)&d_gains, sizeof(float) * ng)); fr.v.push_back(d_gains);
+		HIPCHK(hipMemcpyAsync(d_gains, gains, sizeof(float) * ng, hipMemcpyHostToDevice, st));
 	}
 	op_canvas* cv = new op_canvas;
 	cv->h = H; cv->w = W; cv->device = ctx->device;
@@ -1024,8 +1163,9 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	pool_free(cv->data); delete cv; return OP_ERR_HIP; } } while (0)
 	if (cfg->MULTIBAND <= 0) {
 		ProfScope ps(ctx, "blend linear");
-		if (d_gains) hipLaunchKernelGGL(k_blend_linear<true>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains);
-		else hipLaunchKernelGGL(k_blend_linear<false>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, nullptr);
+		if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_blend_linear<GAIN_BLOCK>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
+		else if (gm == GAIN_IMAGE) hipLaunchKernelGGL(k_blend_linear<GAIN_IMAGE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, 0, 0);
+		else hipLaunchKernelGGL(k_blend_linear<GAIN_NONE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, nullptr, 0, 0);
 		BCHK(hipGetLastError());
 	} else {
 		const int L = cfg->MULTIBAND;
@@ -1042,8 +1182,9 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 		const dim3 rgrid((unsigned)((max_roi + 255) / 256), n);
 		{ ProfScope ps(ctx, "multiband first level");
 		  const dim3 fgrid((W + 1 + 63) / 64, (H + 1 + 3) / 4);
-		  if (d_gains) hipLaunchKernelGGL(k_mb_first_fused<true>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains);
-		  else hipLaunchKernelGGL(k_mb_first_fused<false>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, nullptr);
+		  if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_mb_first_fused<GAIN_BLOCK>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, gbx, gby);
+		  else if (gm == GAIN_IMAGE) hipLaunchKernelGGL(k_mb_first_fused<GAIN_IMAGE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, 0, 0);
+		  else hipLaunchKernelGGL(k_mb_first_fused<GAIN_NONE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, nullptr, 0, 0);
 		  BCHK(hipGetLastError()); }
 		bool band0_done = false;                 // level 0's band written by the fused blur
 		for (int level = 0; level < L; ++level) {
@@ -1106,7 +1247,7 @@ extern "C" {
 
 int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, op_canvas** out) {
 	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend: bad argument");
-	return blend_impl(ctx, cfg, g, imgs, n, nullptr, "op_blend", out);
+	return blend_impl(ctx, cfg, g, imgs, n, nullptr, 0, 0, "op_blend", out);
 }
 
 int op_blend_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains, op_canvas** out) {
@@ -1115,7 +1256,18 @@ int op_blend_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, co
 		for (int e = 0; e < 3 * n; ++e)
 			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
 				OP_FAIL(OP_ERR_INVALID, "op_blend_gains: gain " + std::to_string(e) + " (image " + std::to_string(e / 3) + ") is not finite and positive");
-	return blend_impl(ctx, cfg, g, imgs, n, gains, "op_blend_gains", out);
+	return blend_impl(ctx, cfg, g, imgs, n, gains, 0, 0, "op_blend_gains", out);
+}
+
+int op_blend_block_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int bx, int by,
+		const float* gains, op_canvas** out) {
+	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS)
+		OP_FAIL(OP_ERR_INVALID, "op_blend_block_gains: bad argument");
+	if (gains)
+		for (long long e = 0; e < 3ll * n * bx * by; ++e)
+			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
+				OP_FAIL(OP_ERR_INVALID, "op_blend_block_gains: gain " + std::to_string(e) + " (image " + std::to_string(e / (3 * bx * by)) + ") is not finite and positive");
+	return blend_impl(ctx, cfg, g, imgs, n, gains, bx, by, "op_blend_block_gains", out);
 }
 
 int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
@@ -1164,6 +1316,40 @@ int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, c
 	return OP_OK;
 }
 
+}	// extern "C"
+
+namespace {
+// The dense solve of op_gain_solve and op_gain_block_solve: A = L L^T in place (lower triangle), then L y = rhs,
+// L^T g = y; rhs receives g.  fp64, fixed loop order.  false: A is not positive definite.
+bool gain_cholesky_solve(std::vector<double>& A, std::vector<double>& rhs, int m) {
+	for (int j = 0; j < m; ++j) {
+		double d = A[(size_t)j * m + j];
+		for (int k = 0; k < j; ++k) d -= A[(size_t)j * m + k] * A[(size_t)j * m + k];
+		if (!(d > 0)) return false;
+		const double l = std::sqrt(d);
+		A[(size_t)j * m + j] = l;
+		for (int i = j + 1; i < m; ++i) {
+			double v = A[(size_t)i * m + j];
+			for (int k = 0; k < j; ++k) v -= A[(size_t)i * m + k] * A[(size_t)j * m + k];
+			A[(size_t)i * m + j] = v / l;
+		}
+	}
+	for (int i = 0; i < m; ++i) {
+		double v = rhs[i];
+		for (int k = 0; k < i; ++k) v -= A[(size_t)i * m + k] * rhs[k];
+		rhs[i] = v / A[(size_t)i * m + i];
+	}
+	for (int i = m - 1; i >= 0; --i) {
+		double v = rhs[i];
+		for (int k = i + 1; k < m; ++k) v -= A[(size_t)k * m + i] * rhs[k];
+		rhs[i] = v / A[(size_t)i * m + i];
+	}
+	return true;
+}
+}	// namespace
+
+extern "C" {
+
 // Gain compensation (Brown & Lowe, IJCV 2007, section 6), host only: minimise
 //   e = 1/2 sum_a sum_{b != a} N_ab [ (g_a I_ab - g_b I_ba)^2 / sigma_n^2 + (1 - g_a)^2 / sigma_g^2 ]
 // through its normal equations (for every a, over b != a)
@@ -1210,34 +1396,145 @@ int op_gain_solve(int n, const int64_t* count, const int64_t* sums, double sigma
 				rhs[sa] += N * inv_g2;
 				rhs[sb] += N * inv_g2;
 			}
-		// A = L L^T in place (lower triangle), then L y = rhs, L^T g = y
-		for (int j = 0; j < m; ++j) {
-			double d = A[(size_t)j * m + j];
-			for (int k = 0; k < j; ++k) d -= A[(size_t)j * m + k] * A[(size_t)j * m + k];
-			if (!(d > 0)) OP_FAIL(OP_ERR_INVALID, "op_gain_solve: system not positive definite (inconsistent statistics)");
-			const double l = std::sqrt(d);
-			A[(size_t)j * m + j] = l;
-			for (int i = j + 1; i < m; ++i) {
-				double v = A[(size_t)i * m + j];
-				for (int k = 0; k < j; ++k) v -= A[(size_t)i * m + k] * A[(size_t)j * m + k];
-				A[(size_t)i * m + j] = v / l;
-			}
-		}
-		for (int i = 0; i < m; ++i) {
-			double v = rhs[i];
-			for (int k = 0; k < i; ++k) v -= A[(size_t)i * m + k] * rhs[k];
-			rhs[i] = v / A[(size_t)i * m + i];
-		}
-		for (int i = m - 1; i >= 0; --i) {
-			double v = rhs[i];
-			for (int k = i + 1; k < m; ++k) v -= A[(size_t)k * m + i] * rhs[k];
-			rhs[i] = v / A[(size_t)i * m + i];
-		}
+		if (!gain_cholesky_solve(A, rhs, m)) OP_FAIL(OP_ERR_INVALID, "op_gain_solve: system not positive definite (inconsistent statistics)");
 		for (int i = 0; i < m; ++i) {
 			const float gv = (float)rhs[i];
 			if (per_channel) gains[3 * act[i] + ch] = gv;
 			else gains[3 * act[i]] = gains[3 * act[i] + 1] = gains[3 * act[i] + 2] = gv;
 		}
+	}
+	return OP_OK;
+}
+
+int op_gain_block_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
+		int bx, int by, int64_t* count, int64_t* sums) {
+	if (!ctx || !cfg || !g || !imgs || n < 1 || stride < 1 || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS ||
+			(n > 1 && (!count || !sums)))
+		OP_FAIL(OP_ERR_INVALID, "op_gain_block_overlap: bad argument");
+	int rc = check_blend_args("op_gain_block_overlap", g);
+	if (rc != OP_OK) return rc;
+	const int words = (n + 63) / 64;
+	if (words > GAIN_MAX_IMAGES / 64) OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
+	const long long npairs = (long long)n * (n - 1) / 2, nblk = (long long)bx * by, entries = npairs * nblk * nblk;
+	if (entries > GAIN_BLOCK_MAX_ENTRIES)
+		OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_overlap: " + std::to_string(entries) + " unit-pair entries (pairs x (bx by)^2) exceed " +
+		        std::to_string(GAIN_BLOCK_MAX_ENTRIES));
+	if (npairs == 0) return OP_OK;
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	int H, W;
+	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
+	if (rc != OP_OK) return rc;
+	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, "op_gain_block_overlap: empty canvas");
+	Freer fr;
+	std::vector<BlendImg> h_imgs;
+	long long roi_total = 0, max_roi = 0;
+	BlendImg* d_imgs = nullptr;
+	rc = upload_images(ctx, "op_gain_block_overlap", g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
+	if (rc != OP_OK) return rc;
+	unsigned long long* d_stats = nullptr;         // entries counts, then entries x 6 sums
+	const size_t stat_bytes = sizeof(unsigned long long) * 7 * (size_t)entries;
+	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
+	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
+	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
+	BlendTrig trig{nullptr, nullptr, 0, 0};
+	if (bg.method != 0) {
+		HostScope hs(ctx, "blend trig tables (host)");
+		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
+	}
+	stride = std::min(stride, std::max(H, W));
+	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
+	{ ProfScope ps(ctx, "gain block overlap");
+	  hipLaunchKernelGGL(k_gain_block_overlap, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * words, st,
+	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, bx, by, d_stats, d_stats + entries);
+	  HIPCHK(hipGetLastError()); }
+	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)entries, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(sums, d_stats + entries, sizeof(int64_t) * 6 * (size_t)entries, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	resolve_profile(ctx);
+	return OP_OK;
+}
+
+// Block gain compensation, host only: op_gain_solve's normal equations over units (k, q) -- entry e = p B^2 + qa B + qb
+// couples unit (a, qa) with (b, qb) exactly as pair p couples a with b there, in the same pair order -- plus, for every
+// 4-neighbour edge q ~ q' of an active image k, 2 lambda_k / sigma_s^2 on both diagonals and -2 lambda_k / sigma_s^2 off
+// them, lambda_k = M_k / B, M_k = the overlap samples of k over all its pairs.  With B = 1 there are no edges and the
+// matrix is op_gain_solve's, built in the same order and solved by the same code: the same floats.
+int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, double sigma_s,
+		int per_channel, float* gains) {
+	if (n < 1 || !gains || (n > 1 && (!count || !sums)) || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS ||
+			!(sigma_n > 0) || !(sigma_g > 0) || !(sigma_s > 0) || !std::isfinite(sigma_n) || !std::isfinite(sigma_g) || !std::isfinite(sigma_s) ||
+			(per_channel != 0 && per_channel != 1))
+		OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: bad argument");
+	const int B = bx * by;
+	if ((long long)n * B > GAIN_BLOCK_MAX_UNKNOWNS)
+		OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_solve: " + std::to_string((long long)n * B) + " units (n bx by) exceed the dense solve's " +
+		        std::to_string(GAIN_BLOCK_MAX_UNKNOWNS));
+	const long long npairs = (long long)n * (n - 1) / 2, B2 = (long long)B * B, entries = npairs * B2;
+	for (long long e = 0; e < entries; ++e)
+		if (count[e] < 0) OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: negative overlap count at entry " + std::to_string(e));
+	// the active images (any overlap) in index order, and M_k
+	std::vector<int> slot(n, -1), act;
+	std::vector<double> M(n, 0.0);
+	for (int a = 0; a < n; ++a)
+		for (int b = a + 1; b < n; ++b) {
+			const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+			int64_t N = 0;
+			for (long long e = p * B2; e < (p + 1) * B2; ++e) N += count[e];
+			if (N > 0) { slot[a] = slot[b] = 0; M[a] += (double)N; M[b] += (double)N; }
+		}
+	for (int a = 0; a < n; ++a) if (slot[a] == 0) { slot[a] = (int)act.size(); act.push_back(a); }
+	const int m = (int)act.size() * B;
+	for (long long e = 0; e < 3ll * n * B; ++e) gains[e] = 1.f;
+	if (m == 0) return OP_OK;
+	const double inv_n2 = 1.0 / (sigma_n * sigma_n), inv_g2 = 1.0 / (sigma_g * sigma_g), inv_s2 = 1.0 / (sigma_s * sigma_s);
+	std::vector<double> A((size_t)m * m), rhs(m);
+	const int nsolve = per_channel ? 3 : 1;
+	for (int ch = 0; ch < nsolve; ++ch) {
+		std::fill(A.begin(), A.end(), 0.0); std::fill(rhs.begin(), rhs.end(), 0.0);
+		for (int a = 0; a < n; ++a)
+			for (int b = a + 1; b < n; ++b) {
+				const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+				for (int qa = 0; qa < B; ++qa)
+					for (int qb = 0; qb < B; ++qb) {
+						const long long e = p * B2 + (long long)qa * B + qb;
+						if (count[e] <= 0) continue;
+						const double N = (double)count[e], den = GAIN_FIX * N;
+						const int64_t* S = sums + 6 * e;
+						double Iab, Iba;
+						if (per_channel) { Iab = (double)S[ch] / den; Iba = (double)S[3 + ch] / den; }
+						else { Iab = ((double)(S[0] + S[1] + S[2]) / 3.0) / den; Iba = ((double)(S[3] + S[4] + S[5]) / 3.0) / den; }
+						const int sa = slot[a] * B + qa, sb = slot[b] * B + qb;
+						A[(size_t)sa * m + sa] += N * (2.0 * Iab * Iab * inv_n2 + inv_g2);
+						A[(size_t)sb * m + sb] += N * (2.0 * Iba * Iba * inv_n2 + inv_g2);
+						const double off = N * (2.0 * Iab * Iba * inv_n2);
+						A[(size_t)sa * m + sb] -= off;
+						A[(size_t)sb * m + sa] -= off;
+						rhs[sa] += N * inv_g2;
+						rhs[sb] += N * inv_g2;
+					}
+			}
+		for (int s = 0; s < (int)act.size(); ++s) {       // smoothness: the grid Laplacian of every active image
+			const double w = 2.0 * (M[act[s]] / B) * inv_s2;
+			for (int v = 0; v < by; ++v)
+				for (int u = 0; u < bx; ++u) {
+					const int q = s * B + v * bx + u;
+					for (int d = 0; d < 2; ++d) {
+						if (d == 0 ? u + 1 >= bx : v + 1 >= by) continue;
+						const int q2 = q + (d == 0 ? 1 : bx);
+						A[(size_t)q * m + q] += w; A[(size_t)q2 * m + q2] += w;
+						A[(size_t)q * m + q2] -= w; A[(size_t)q2 * m + q] -= w;
+					}
+				}
+		}
+		if (!gain_cholesky_solve(A, rhs, m)) OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: system not positive definite (inconsistent statistics)");
+		for (int s = 0; s < (int)act.size(); ++s)
+			for (int q = 0; q < B; ++q) {
+				const float gv = (float)rhs[(size_t)s * B + q];
+				float* o = gains + 3 * ((long long)act[s] * B + q);
+				if (per_channel) o[ch] = gv;
+				else o[0] = o[1] = o[2] = gv;
+			}
 	}
 	return OP_OK;
 }

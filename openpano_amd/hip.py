@@ -204,6 +204,13 @@ def lib():
         L.op_gain_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]
         L.op_blend_gains.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
                                      C.c_void_p, C.POINTER(C.c_void_p)]
+    if hasattr(L, "op_gain_block_overlap"):
+        L.op_gain_block_overlap.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.op_gain_block_solve.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                          C.c_int, C.c_void_p]
+        L.op_blend_block_gains.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
+                                           C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
@@ -786,12 +793,19 @@ def blend_prepare(cfg, shapes_wh, homos, proj_method, identity_idx):
 
 GAIN_FIX = 2.0 ** 32                  # fixed-point scale of op_gain_overlap's colour sums
 GAIN_SIGMA_N, GAIN_SIGMA_G = 10.0 / 255.0, 0.1
+GAIN_SIGMA_S = 0.1                    # smoothness of block gains (op_gain_block_solve)
+GAIN_BLOCK_MAX_ENTRIES = 1 << 22      # op_gain_block_overlap's cap on pairs x (bx by)^2 (include/openpano_hip.h)
 
 
 def _gains_array(gains, n):
+    """(n, 3) per-image gains, or (n, by, bx, 3) block gains (4-d); (n,) = one gain per image"""
     if gains is None:
         return None
     g = np.ascontiguousarray(np.asarray(gains, np.float32))
+    if g.ndim == 4:
+        if g.shape[0] != n or g.shape[3] != 3:
+            raise ValueError(f"block gains must be ({n}, by, bx, 3), got {g.shape}")
+        return g
     if g.size == n:                    # one gain per image: all three channels
         g = np.ascontiguousarray(np.repeat(g.reshape(n, 1), 3, axis=1))
     if g.shape != (n, 3):
@@ -802,7 +816,7 @@ def _gains_array(gains, n):
 class BlendCall:
     """``ConnectedImages::blend()`` (stitcher_image.cc:116-155) with the op_blend_geom / op_blend_image arrays marshalled
     once, like a C host holds them; every call is one op_blend -- or, with ``gains`` ((n, 3) or (n,) exposure gains), one
-    op_blend_gains.
+    op_blend_gains; with (n, by, bx, 3) block gains, one op_blend_block_gains.
     images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo."""
 
     def __init__(self, ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None):
@@ -826,6 +840,10 @@ class BlendCall:
         h = C.c_void_p()
         if self.gains is None:
             check(self._fn(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, C.byref(h)))
+        elif self.gains.ndim == 4:
+            by, bx = self.gains.shape[1:3]
+            check(lib().op_blend_block_gains(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(bx), int(by),
+                                             self.gains.ctypes.data_as(C.c_void_p), C.byref(h)))
         else:
             check(lib().op_blend_gains(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n,
                                        self.gains.ctypes.data_as(C.c_void_p), C.byref(h)))
@@ -840,11 +858,25 @@ class BlendCall:
                                     count.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
         return count[:npairs], sums[:npairs]
 
+    def block_overlap_sums(self, bx, by, stride=1):
+        """op_gain_block_overlap -> (count (P, B, B) int64, sums (P, B, B, 6) int64 fixed point), B = bx * by: the entry
+        [p, qa, qb] holds the samples of pair p = pair_index(n, a, b) whose a-side lies in block qa = v * bx + u of image a
+        and b-side in block qb of image b."""
+        npairs, B = self.n * (self.n - 1) // 2, int(bx) * int(by)
+        if npairs * B * B > GAIN_BLOCK_MAX_ENTRIES:       # refused by the library; do not allocate the arrays first
+            raise OpenPanoHipError(f"op_gain_block_overlap: {npairs * B * B} unit-pair entries exceed {GAIN_BLOCK_MAX_ENTRIES}")
+        rows = max(npairs, 1)
+        count = np.zeros((rows, B, B), np.int64); sums = np.zeros((rows, B, B, 6), np.int64)
+        check(lib().op_gain_block_overlap(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(stride),
+                                          int(bx), int(by), count.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
+        return count[:npairs], sums[:npairs]
+
 
 def blend(ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None) -> Canvas:
     """``ConnectedImages::blend()`` (stitcher_image.cc:116-155) on the device.
     images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo.
-    gains: optional (n, 3) or (n,) exposure gains (op_blend_gains); None = op_blend."""
+    gains: optional (n, 3) or (n,) exposure gains (op_blend_gains), or (n, by, bx, 3) block gains (op_blend_block_gains);
+    None = op_blend."""
     return BlendCall(ctx, cfg, images, homos, proj_method, identity_idx, gains=gains)()
 
 
@@ -885,6 +917,28 @@ def gain_compensate(ctx: Context, cfg, images, homos, proj_method, identity_idx,
     """op_gain_overlap + op_gain_solve: the exposure gains (n, 3) to pass to blend(..., gains=)"""
     count, sums = gain_overlap_sums(ctx, cfg, images, homos, proj_method, identity_idx, stride)
     return gain_solve(len(images), count, sums, sigma_n, sigma_g, per_channel)
+
+
+def gain_block_solve(n, bx, by, count, sums, sigma_n=GAIN_SIGMA_N, sigma_g=GAIN_SIGMA_G, sigma_s=GAIN_SIGMA_S, per_channel=True):
+    """op_gain_block_solve (host only): block gains (n, by, bx, 3) float32 from op_gain_block_overlap's count / sums"""
+    npairs, B = n * (n - 1) // 2, int(bx) * int(by)
+    c = np.ascontiguousarray(np.asarray(count, np.int64).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(sums, np.int64).reshape(-1))
+    if len(c) != npairs * B * B or len(s) != 6 * npairs * B * B:
+        raise ValueError(f"{n} images at {bx} x {by} need {npairs * B * B} entries, got {len(c)} counts and {len(s) // 6} sums")
+    out = np.zeros((n, int(by), int(bx), 3), np.float32)
+    check(lib().op_gain_block_solve(int(n), int(bx), int(by), c.ctypes.data_as(C.c_void_p) if npairs else None,
+                                    s.ctypes.data_as(C.c_void_p) if npairs else None, float(sigma_n), float(sigma_g), float(sigma_s),
+                                    int(bool(per_channel)), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def gain_block_compensate(ctx: Context, cfg, images, homos, proj_method, identity_idx, bx, by, stride=1, sigma_n=GAIN_SIGMA_N,
+                          sigma_g=GAIN_SIGMA_G, sigma_s=GAIN_SIGMA_S, per_channel=True):
+    """op_gain_block_overlap + op_gain_block_solve: the block gains (n, by, bx, 3) to pass to blend(..., gains=)"""
+    call = BlendCall(ctx, cfg, images, homos, proj_method, identity_idx)
+    count, sums = call.block_overlap_sums(bx, by, stride)
+    return gain_block_solve(len(images), bx, by, count, sums, sigma_n, sigma_g, sigma_s, per_channel)
 
 
 def cyl_warp_shape(cfg, w, h, h_factor, pts=None):

@@ -641,10 +641,29 @@ inline std::vector<float> hip_gain_compensate(const Bundle& b, int stride = 1, d
 	PANO_HIP_CHECK(op_gain_solve(n, count.data(), sums.data(), sigma_n, sigma_g, per_channel ? 1 : 0, gains.data()));
 	return gains;
 }
-
-// gains: empty = op_blend, else n x 3 exposure gains (op_blend_gains)
+// Block gain compensation (the C-ABI's op_gain_block_overlap + op_gain_block_solve): one gain per block of a bx x by grid
+// on every image, which also evens out vignetting and brightness gradients inside a view.  Returns n * by * bx * 3 gains,
+// [((k * by + v) * bx + u) * 3 + c]; pass them to hip_blend(b, crop, gains, bx, by).
 template <typename Bundle>
-inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains) {
+inline std::vector<float> hip_gain_compensate_blocks(const Bundle& b, int bx, int by, int stride = 1, double sigma_n = 10.0 / 255.0,
+		double sigma_g = 0.1, double sigma_s = 0.1, bool per_channel = true) {
+	op_ctx* ctx = HipContext::get();
+	const op_config cfg = hip_config_snapshot();
+	const int n = (int)b.component.size();
+	op_blend_geom g;
+	const std::vector<op_blend_image> ims = hip_blend_images(b, g);
+	const size_t B = (size_t)bx * by, entries = (size_t)n * (n - 1) / 2 * B * B;
+	std::vector<int64_t> count(entries + 1), sums(6 * entries + 1);
+	std::vector<float> gains(3 * (size_t)n * B);
+	PANO_HIP_CHECK(op_gain_block_overlap(ctx, &cfg, &g, ims.data(), n, stride, bx, by, count.data(), sums.data()));
+	PANO_HIP_CHECK(op_gain_block_solve(n, bx, by, count.data(), sums.data(), sigma_n, sigma_g, sigma_s, per_channel ? 1 : 0, gains.data()));
+	return gains;
+}
+
+// gains: empty = op_blend; bx = by = 0: n x 3 exposure gains (op_blend_gains); bx, by >= 1: n x by x bx x 3 block gains
+// (op_blend_block_gains)
+template <typename Bundle>
+inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains, int bx, int by) {
 	op_ctx* ctx = HipContext::get();
 	const op_config cfg = hip_config_snapshot();
 	const int n = (int)b.component.size();
@@ -657,9 +676,11 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 	}
 #endif
 	const std::vector<op_blend_image> ims = hip_blend_images(b, g);
-	if (!gains.empty() && gains.size() != (size_t)3 * n) { fprintf(stderr, "hip_blend: %zu gains for %d images\n", gains.size(), n); exit(1); }
+	const size_t per_image = bx > 0 ? (size_t)3 * bx * by : 3;
+	if (!gains.empty() && gains.size() != per_image * n) { fprintf(stderr, "hip_blend: %zu gains for %d images\n", gains.size(), n); exit(1); }
 	op_canvas* cv = nullptr;
 	if (gains.empty()) PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
+	else if (bx > 0) PANO_HIP_CHECK(op_blend_block_gains(ctx, &cfg, &g, ims.data(), n, bx, by, gains.data(), &cv));
 	else PANO_HIP_CHECK(op_blend_gains(ctx, &cfg, &g, ims.data(), n, gains.data(), &cv));
 	if (crop) {
 		op_canvas* cc = nullptr;
@@ -675,6 +696,9 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 	return out;
 }
 
+// gains: empty = op_blend, else n x 3 exposure gains (op_blend_gains)
+template <typename Bundle>
+inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains) { return hip_blend(b, crop, gains, 0, 0); }
 template <typename Bundle>
 inline Mat32f hip_blend(const Bundle& b, bool crop = false) { return hip_blend(b, crop, std::vector<float>()); }
 
@@ -805,8 +829,12 @@ class HipStitcher {
 			bundle.proj_method = config::ESTIMATE_CAMERA ? ConnectedImages::spherical : ConnectedImages::flat;
 			bundle.update_proj_range();
 			if (!gain_compensation) { gains.clear(); return bundle.blend(); }
-			gains = hip_gain_compensate(bundle);                    // after the homographies are final
-			return hip_blend(bundle, false, gains);
+			if (gain_blocks_x == 1 && gain_blocks_y == 1) {
+				gains = hip_gain_compensate(bundle);                // after the homographies are final
+				return hip_blend(bundle, false, gains);
+			}
+			gains = hip_gain_compensate_blocks(bundle, gain_blocks_x, gain_blocks_y);
+			return hip_blend(bundle, false, gains, gain_blocks_x, gain_blocks_y);
 		}
 
 		std::vector<ImageRef> imgs;
@@ -817,8 +845,10 @@ class HipStitcher {
 		std::vector<Camera> cameras;
 		uint32_t base_seed;
 		// exposure (gain) compensation before the blend (hip_gain_compensate): an extension, off by default; `gains` holds
-		// the n x 3 gains the last build() used (empty when it used none)
+		// the n x 3 gains the last build() used (empty when it used none).  gain_blocks_x / _y > 1: one gain per block of
+		// that grid on every image (hip_gain_compensate_blocks); `gains` then holds n * by * bx * 3
 		bool gain_compensation = false;
+		int gain_blocks_x = 1, gain_blocks_y = 1;
 		std::vector<float> gains;
 
 		void calc_feature() {                                       // stitcherbase.cc:9-27

@@ -12,9 +12,12 @@
 // (pano_camera.hh), spherical blend; out.bin then carries n*13 f64 cameras (focal, aspect, ppx,
 // ppy, R) in place of the chain homographies, before the canvas.
 // "camera_build": the same branch through HipStitcher::build() itself (Stitcher st(mats); st.build()); out.bin then
-// holds only int32 H, W ; H*W*3 f32 [; n*3 f32 gains under --gain-compensation].
+// holds only int32 H, W ; H*W*3 f32 [; n*3 f32 gains under --gain-compensation, n*B*3 under --gain-blocks].
 // --gain-compensation (anywhere on the line): exposure compensation before the blend (HipStitcher::gain_compensation,
 // hip_gain_compensate: an extension beyond the reference); out.bin then ends with n*3 f32 gains after the canvas.
+// --gain-blocks BXxBY (anywhere; implies --gain-compensation): block gain compensation on a BX x BY grid per image
+// (HipStitcher::gain_blocks_x / _y, hip_gain_compensate_blocks; 1x1 is --gain-compensation itself); out.bin then ends
+// with n*BY*BX*3 f32 gains, [((k*BY + v)*BX + u)*3 + c], after the canvas (camera modes) or the chain homographies.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
@@ -74,7 +77,7 @@ static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::
 
 // Stitcher::build() under ESTIMATE_CAMERA (stitch/stitcher.cc:32-64), stage by stage so that every
 // intermediate can be written out
-static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain) {
+static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby) {
 	Stitcher st(mats, base_seed);
 	FILE* fo = fopen(out_path, "wb");
 	if (!fo) { perror(out_path); return 2; }
@@ -100,23 +103,27 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 	}
 	st.bundle.proj_method = ConnectedImages::spherical;
 	st.bundle.update_proj_range();
-	if (gain) st.gains = hip_gain_compensate(st.bundle);          // what HipStitcher::build() does under gain_compensation
-	Mat32f pano = gain ? hip_blend(st.bundle, false, st.gains) : st.bundle.blend();
+	const bool blocks = gain && gbx * gby > 1;
+	if (blocks) st.gains = hip_gain_compensate_blocks(st.bundle, gbx, gby);   // what HipStitcher::build() does under gain_blocks_x / _y
+	else if (gain) st.gains = hip_gain_compensate(st.bundle);     // what HipStitcher::build() does under gain_compensation
+	Mat32f pano = blocks ? hip_blend(st.bundle, false, st.gains, gbx, gby) : gain ? hip_blend(st.bundle, false, st.gains) : st.bundle.blend();
 	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
 	if (gain) {
 		put(fo, st.gains.data(), st.gains.size());
-		for (int k = 0; k < n; ++k) fprintf(stderr, "gain %d: %g %g %g\n", k, st.gains[3 * k], st.gains[3 * k + 1], st.gains[3 * k + 2]);
+		const size_t per = st.gains.size() / n;      // 3 per image, or 3 per block
+		for (int k = 0; k < n; ++k) fprintf(stderr, "gain %d: %g %g %g\n", k, st.gains[per * k], st.gains[per * k + 1], st.gains[per * k + 2]);
 	}
 	fclose(fo);
 	return 0;
 }
 
 // Stitcher::build() as a client calls it, gain compensation per HipStitcher::gain_compensation
-static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain) {
+static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain, int gbx, int gby) {
 	Stitcher st(mats, base_seed);
 	st.gain_compensation = gain;
+	st.gain_blocks_x = gbx; st.gain_blocks_y = gby;
 	Mat32f pano = st.build();
 	FILE* fo = fopen(out_path, "wb");
 	if (!fo) { perror(out_path); return 2; }
@@ -130,15 +137,22 @@ static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint
 
 int main(int argc, char** argv) {
 	bool gain = false;
-	{	// --gain-compensation may stand anywhere; the positional arguments keep their places
+	int gbx = 1, gby = 1;
+	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
 			if (std::string(argv[k]) == "--gain-compensation") gain = true;
+			else if (std::string(argv[k]) == "--gain-blocks" && k + 1 < argc) {
+				if (sscanf(argv[++k], "%dx%d", &gbx, &gby) != 2 || gbx < 1 || gbx > 16 || gby < 1 || gby > 16) {
+					fprintf(stderr, "--gain-blocks wants BXxBY, each in [1, 16]; got %s\n", argv[k]); return 2;
+				}
+				gain = true;
+			}
 			else argv[m++] = argv[k];
 		}
 		argc = m;
 	}
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY]\n", argv[0]); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
@@ -155,8 +169,8 @@ int main(int argc, char** argv) {
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
-	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain);
-	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain);
+	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby);
+	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby);
 
 	// ---- StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27)
 	std::vector<ImageRef> imgs;
@@ -221,8 +235,9 @@ int main(int argc, char** argv) {
 		}
 		bundle.calc_inverse_homo();
 		bundle.update_proj_range();
-		const std::vector<float> gains = gain ? hip_gain_compensate(bundle) : std::vector<float>();
-		Mat32f pano = hip_blend(bundle, false, gains);
+		const bool blocks = gain && gbx * gby > 1;
+		const std::vector<float> gains = blocks ? hip_gain_compensate_blocks(bundle, gbx, gby) : gain ? hip_gain_compensate(bundle) : std::vector<float>();
+		Mat32f pano = blocks ? hip_blend(bundle, false, gains, gbx, gby) : hip_blend(bundle, false, gains);
 		put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 		put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 		for (auto& t : to_mid) put(fo, t.data, 9);

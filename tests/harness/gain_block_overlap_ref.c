@@ -1,0 +1,136 @@
+/* gain_block_overlap_ref.c -- CPU restatements of the block gain entry points (openpano_amd/csrc/blend.hip) for
+ * tests/test_gpu_gain_blocks.py, built like gain_overlap_ref.c (included below for its image type, interpolate() and
+ * sampling rules) with -ffp-contract=off so that every fp64 / fp32 operation is the device's:
+ *   gain_block_overlap_ref  op_gain_block_overlap (k_gain_block_overlap): op_gain_overlap's statistics split by block pair,
+ *                           entry e = p * B^2 + qa * B + qb;
+ *   blend_linear_block_ref  op_blend_block_gains with the linear blender (k_blend_linear<GAIN_BLOCK>): every valid sample
+ *                           scaled by the block-centre gains interpolated at the sample, both LAZY_READ branches. */
+#include "gain_overlap_ref.c"
+
+/* the canvas -> space map of ConnectedImages::blend at (i, j), the per-column / per-row transcendentals from this libm */
+static void map_point(int method, double minx, double miny, double resx, double resy, int i, int j, double* hx, double* hy, double* hz) {
+	if (method == 0) { *hx = (double)j * resx + minx; *hy = (double)i * resy + miny; *hz = 1.0; }
+	else {
+		const double x = (double)j * resx + minx, y = (double)i * resy + miny;
+		*hx = sin(x); *hz = cos(x); *hy = method == 2 ? tan(y) : y;
+	}
+}
+
+/* sample() with the image coordinates (r, c) it interpolates at */
+static int sample_rc(const gref_image* im, int i, int j, double hx, double hy, double hz, int lazy, float* r, float* c, float col[3]) {
+	const int in = lazy ? (i >= im->y0 && i < im->y1 && j >= im->x0 && j < im->x1)
+	                    : (i >= im->y0 && i <= im->y1 && j >= im->x0 && j <= im->x1);
+	if (!in) return 0;
+	const double* d = im->hinv;
+	const double rx = d[0] * hx + d[1] * hy + d[2] * hz;
+	const double ry = d[3] * hx + d[4] * hy + d[5] * hz;
+	const double rz = d[6] * hx + d[7] * hy + d[8] * hz;
+	double ox, oy;
+	if (rz < 0) { ox = -10; oy = -10; }
+	else {
+		const double denom = 1.0 / rz;
+		ox = rx * denom + im->w * 0.5;
+		oy = ry * denom + im->h * 0.5;
+	}
+	if (ox < 0 || ox >= im->w || oy < 0 || oy >= im->h) return 0;
+	*r = (float)oy; *c = (float)ox;
+	if (!interp(im->data, im->mh, im->mw, *r, *c, col)) return 0;
+	return !(col[0] < 0);
+}
+
+/* the block of a sample (include/openpano_hip.h) */
+static int block_of(float r, float c, int w, int h, int bx, int by) {
+	int u = (int)floorf(c * (float)bx / (float)w), v = (int)floorf(r * (float)by / (float)h);
+	u = u < 0 ? 0 : (u > bx - 1 ? bx - 1 : u);
+	v = v < 0 ? 0 : (v > by - 1 ? by - 1 : v);
+	return v * bx + u;
+}
+
+/* count: P * B^2, sums: P * B^2 * 6, both zeroed by the caller */
+int gain_block_overlap_ref(int method, double minx, double miny, double resx, double resy, int H, int W, int n, const gref_image* imgs,
+		int stride, int lazy, int bx, int by, int64_t* count, int64_t* sums) {
+	float* col = (float*)malloc(sizeof(float) * 3 * (size_t)n);
+	int* ok = (int*)malloc(sizeof(int) * (size_t)n);
+	int* q = (int*)malloc(sizeof(int) * (size_t)n);
+	if (!col || !ok || !q) return -1;
+	const long long B = (long long)bx * by;
+	for (int i = 0; i < H; i += stride) {
+		for (int j = 0; j < W; j += stride) {
+			double hx, hy, hz;
+			map_point(method, minx, miny, resx, resy, i, j, &hx, &hy, &hz);
+			for (int k = 0; k < n; ++k) {
+				float r, c;
+				ok[k] = sample_rc(&imgs[k], i, j, hx, hy, hz, lazy, &r, &c, col + 3 * k);
+				q[k] = ok[k] ? block_of(r, c, imgs[k].w, imgs[k].h, bx, by) : 0;
+			}
+			for (int a = 0; a < n; ++a) {
+				if (!ok[a]) continue;
+				for (int b = a + 1; b < n; ++b) {
+					if (!ok[b]) continue;
+					const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+					const long long e = p * B * B + q[a] * B + q[b];
+					count[e] += 1;
+					for (int c = 0; c < 3; ++c) {
+						sums[6 * e + c] += llrint((double)col[3 * a + c] * 4294967296.0);
+						sums[6 * e + 3 + c] += llrint((double)col[3 * b + c] * 4294967296.0);
+					}
+				}
+			}
+		}
+	}
+	free(col); free(ok); free(q);
+	return 0;
+}
+
+/* one axis of the block-centre interpolation (include/openpano_hip.h) */
+static void block_axis(float x, int nb, int dim, int* i0, int* i1, float* t) {
+	const float f = x * (float)nb / (float)dim - 0.5f;
+	int a = (int)floorf(f);
+	a = a < 0 ? 0 : (a > nb - 1 ? nb - 1 : a);
+	*i0 = a; *i1 = a + 1 < nb ? a + 1 : nb - 1;
+	const float tt = f - (float)a;
+	*t = tt < 0.f ? 0.f : (tt > 1.f ? 1.f : tt);
+}
+
+/* LinearBlender::run (blender.cc:24-96) with block gains: out H x W x 3; gains n x by x bx x 3 */
+int blend_linear_block_ref(int method, double minx, double miny, double resx, double resy, int H, int W, int n, const gref_image* imgs,
+		int lazy, int ordered_input, int bx, int by, const float* gains, float* out) {
+	for (int i = 0; i < H; ++i) {
+		for (int j = 0; j < W; ++j) {
+			double hx, hy, hz;
+			map_point(method, minx, miny, resx, resy, i, j, &hx, &hy, &hz);
+			float s0 = 0.f, s1 = 0.f, s2 = 0.f, wsum = 0.f;
+			for (int k = 0; k < n; ++k) {
+				const gref_image* im = &imgs[k];
+				float r, c, col[3];
+				if (!sample_rc(im, i, j, hx, hy, hz, lazy, &r, &c, col)) continue;
+				int u0, u1, v0, v1; float tx, ty;
+				block_axis(c, bx, im->w, &u0, &u1, &tx);
+				block_axis(r, by, im->h, &v0, &v1, &ty);
+				const float* G = gains + (size_t)3 * k * bx * by;
+				for (int ch = 0; ch < 3; ++ch) {
+					const float g00 = G[(v0 * bx + u0) * 3 + ch], g01 = G[(v0 * bx + u1) * 3 + ch];
+					const float g10 = G[(v1 * bx + u0) * 3 + ch], g11 = G[(v1 * bx + u1) * 3 + ch];
+					const float top = g00 + tx * (g01 - g00), bot = g10 + tx * (g11 - g10);
+					const float g = top + ty * (bot - top);
+					if (g != 1.f) col[ch] = fminf(col[ch] * g, 1.f);
+				}
+				float w = (float)(0.5 - fabs((double)(c / (float)im->w) - 0.5));
+				if (!ordered_input) w = (float)((double)w * (0.5 - fabs((double)(r / (float)im->h) - 0.5)));
+				s0 += col[0] * w; s1 += col[1] * w; s2 += col[2] * w;
+				wsum += w;
+			}
+			float* row = out + ((size_t)i * W + j) * 3;
+			if (lazy) {
+				if (wsum != 0.f) { row[0] = s0 / wsum; row[1] = s1 / wsum; row[2] = s2 / wsum; }
+				else { row[0] = -1.f; row[1] = -1.f; row[2] = -1.f; }
+			} else {
+				if (wsum > 0) {
+					const float inv = (float)(1.0 / (double)wsum);
+					row[0] = s0 * inv; row[1] = s1 * inv; row[2] = s2 * inv;
+				} else { row[0] = -1.f; row[1] = -1.f; row[2] = -1.f; }
+			}
+		}
+	}
+	return 0;
+}
