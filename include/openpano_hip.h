@@ -411,6 +411,54 @@ int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64
 int op_blend_block_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int bx, int by,
 		const float* gains, op_canvas** out);
 
+/* ---- VIGNETTING COMPENSATION (ABI 11) -- exposure gains plus ONE radial falloff curve shared by all views (one lens, one
+ * zoom and aperture setting), as Goldman (PAMI 2010) and Hugin's photometric optimiser add after Brown & Lowe's gains: a
+ * scene point seen near the edge of one view and near the centre of another constrains the curve, so a panorama-wide
+ * falloff that block gains cannot see is corrected.  Opt-in; a = 0 reduces exactly to op_blend_gains.
+ *
+ * Model.  Image k (op_blend_image h x w, the ImageRef size linear_sample bounds against) has its centre where the map puts
+ * it, (0.5 w, 0.5 h).  A sample at image coordinates (r, c) -- the floats the linear blender passes to interpolate() -- has
+ * the normalised squared radius, in fp32 exactly (fw = (float)w, fh = (float)h),
+ *   dx = c - 0.5f * fw,  dy = r - 0.5f * fh,  rho = fminf((dx * dx + dy * dy) / (0.25f * (fw * fw + fh * fh)), 1.f),
+ * in [0, 1], isotropic in pixels, 1 at the corners; and the grey level Y = (col[0] + col[1] + col[2]) / 3.f.  Observation
+ * model: Y_k(x) = e_k V(rho_k(x)) L(x), V(rho) = 1 + a1 rho + a2 rho^2 + a3 rho^3, achromatic; gains g_k = 1 / e_k are grey.
+ * Views whose mat_h / mat_w are set to another size than h / w (a cylinder pre-warp) are refused with OP_ERR_UNSUPPORTED:
+ * their samples are not in the lens frame.
+ *
+ * op_vignette_overlap: op_gain_overlap's lattice, validity rules and LAZY_READ branches; a sample whose largest channel
+ * exceeds clip (in (0, 1]; 1 keeps every valid sample of an image in [0, 1]) does not take part.  For every pair p (a < b,
+ * index as above) of valid samples, pa[k] = rho_a^k and pb[k] = rho_b^k in fp64 (pa[0] = 1, pa[k] = pa[k-1] * rho_a):
+ *   count[p] += 1,
+ *   moments[30p + k]          = A_k  += (Ya * Ya) * pb[k]            k = 0..6
+ *   moments[30p + 7 + k]      = B_k  += (Yb * Yb) * pa[k]            k = 0..6
+ *   moments[30p + 14 + 4i + j] = C_ij += ((Ya * Yb) * pa[i]) * pb[j]  i, j = 0..3
+ * each product formed in fp64 from the fp32 Y / rho in that order and summed as llrint(x * 2^32) in int64 (bit-equal
+ * between runs).  Every term lies in [0, 1]; at most 2^30 lattice points per call (OP_ERR_UNSUPPORTED beyond: raise the
+ * stride), so no sum can overflow.  count: P, moments: 30 P (both may be NULL when n == 1).
+ * op_vignette_solve (HOST ONLY): gains and the curve minimising, a = (1, a1, a2, a3), H(A) the 4 x 4 Hankel matrix A_{i+j},
+ *   E = sum_p [ (g_a^2 a'H(A)a - 2 g_a g_b a'Ca + g_b^2 a'H(B)a) / sigma_n^2 + N_p ((1 - g_a)^2 + (1 - g_b)^2) / sigma_g^2 ]
+ *     + (sum_p N_p) (a1^2 + a2^2 + a3^2) / sigma_v^2,
+ * the data term being sum (g_a Y_a V(rho_b) - g_b Y_b V(rho_a))^2 over the pair's samples (moments in 2^-32 units).
+ * Alternation from a = 0: g given a (an SPD system with op_gain_solve's pattern), then a1..a_degree given g (the others stay
+ * 0); at most 100 rounds, stopping early when a round lowers E by no more than 1e-12 E.  The gains are then divided by
+ * their overlap-weighted mean sum_p N_p (g_a + g_b) / (2 sum_p N_p): the data term pulls all of them towards 0 where the
+ * overlaps disagree with the model, and this keeps the panorama's brightness (ratios and curve unchanged).  fp64, fixed
+ * order.  degree in [1, 3].  Usual sigma_n = 10/255, sigma_g = 1, sigma_v = 100 (the weak priors a one-row sweep needs).
+ * gains: n x 3, the same gain in all three channels; images without overlap get 1; no overlap at all: a = 0.
+ * poly: a1, a2, a3.  OP_ERR_UNSUPPORTED (gains 1, poly 0 written) when the fitted curve does not stay above 1e-6 on
+ * [0, 1] or a gain is not positive: the caller keeps plain gains.
+ * op_blend_vignette: op_blend with every valid sample (linear blender; multiband level 0) of image k at (r, c) scaled by
+ *   V = 1.f + rho * (a1 + rho * (a2 + rho * a3)),  f_c = gains[3k + c] / V  (fp32),  col[c] = min(col[c] * f_c, 1),
+ * a channel whose f_c is exactly 1 left as it is.  gains NULL = all 1, poly NULL = 0; gains finite and > 0, the curve above
+ * 1e-6 on [0, 1].  a = 0 gives op_blend_gains(gains)'s canvas bit for bit, and with gains 1 op_blend's.
+ * Bad arguments return OP_ERR_INVALID.  Threading and ownership as the per-image entry points. */
+int op_vignette_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
+		float clip, int64_t* count, int64_t* moments);
+int op_vignette_solve(int n, const int64_t* count, const int64_t* moments, int degree, double sigma_n, double sigma_g, double sigma_v,
+		float* gains, float* poly);
+int op_blend_vignette(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
+		const float* poly, op_canvas** out);
+
 /* CYLINDER mode pre-warp -- replaces CylinderWarper::warp (stitch/warp.hh:47-55, warp.cc:13-75).
  * op_cyl_warp_shape is the host part (projector, output shape, offset and the keypoints, which
  * are centred coordinates updated in place: warp.cc:46-67); op_cyl_warp renders the pixels. */

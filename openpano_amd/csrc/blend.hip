@@ -197,9 +197,31 @@ __device__ __forceinline__ void apply_block_gain(const float* __restrict__ G, in
 	}
 }
 
+// Radial vignetting shared by all views (op_vignette_overlap / op_blend_vignette): the normalised squared radius of a sample
+// at image coordinates (r, c) of an image of ImageRef size w x h about the map's centre (0.5 w, 0.5 h) -- isotropic in
+// pixels, 1 at the corners, clamped to [0, 1] against rounding -- and the grey level the model observes.  Both exact fp32
+// expressions are part of the contract (include/openpano_hip.h); the CPU restatements copy them.
+constexpr int GAIN_VIGNETTE = 3;
+__device__ __forceinline__ float vignette_rho(float r, float c, int w, int h) {
+	const float fw = (float)w, fh = (float)h;
+	const float dx = c - 0.5f * fw, dy = r - 0.5f * fh;
+	return fminf((dx * dx + dy * dy) / (0.25f * (fw * fw + fh * fh)), 1.f);
+}
+__device__ __forceinline__ float vignette_grey(const float (&col)[3]) { return (col[0] + col[1] + col[2]) / 3.f; }
+// The gains g (3 floats) divided by the curve V = 1 + rho (a1 + rho (a2 + rho a3)) at the sample (poly = a1, a2, a3), then
+// applied per channel as apply_gain does: a = 0 gives V = 1 exactly, so it reproduces apply_gain bit for bit.
+__device__ __forceinline__ void apply_vignette(const float* __restrict__ g, const float* __restrict__ poly, int w, int h, float r, float c,
+		float (&col)[3]) {
+	const float rho = vignette_rho(r, c, w, h);
+	const float V = 1.f + rho * (poly[0] + rho * (poly[1] + rho * poly[2]));
+#pragma unroll
+	for (int ch = 0; ch < 3; ++ch) { const float f = g[ch] / V; if (f != 1.f) col[ch] = fminf(col[ch] * f, 1.f); }
+}
+
 // ---- LinearBlender::run (blender.cc:24-96): thread per canvas pixel, images in index order.  GM: GAIN_IMAGE -- gains
 // (n x 3) scale every sample (op_blend_gains); GAIN_BLOCK -- gains (n x gby x gbx x 3) are interpolated at the sample
-// (op_blend_block_gains); GAIN_NONE -- the kernel is op_blend's.  gbx / gby are read by GAIN_BLOCK only ----
+// (op_blend_block_gains); GAIN_VIGNETTE -- gains (n x 3, then the curve's a1..a3 at gains + 3n) are divided by the shared
+// curve at the sample (op_blend_vignette); GAIN_NONE -- the kernel is op_blend's.  gbx / gby are read by GAIN_BLOCK only ----
 template <int GM>
 __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		float* __restrict__ out, int H, int W, int ordered_input, int lazy, const float* __restrict__ gains, int gbx, int gby) {
@@ -219,6 +241,7 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 			if (!linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col)) return;
 			if (GM == GAIN_IMAGE) apply_gain(gains + 3 * (long long)k, col);
 			if (GM == GAIN_BLOCK) apply_block_gain(gains + 3 * (long long)k * gbx * gby, gbx, gby, im.w, im.h, r, c, col);
+			if (GM == GAIN_VIGNETTE) apply_vignette(gains + 3 * (long long)k, gains + 3 * (long long)n, im.w, im.h, r, c, col);
 			float w = (float)(0.5 - fabs((double)(c / (float)im.w) - 0.5));
 			if (!ordered_input) w = (float)((double)w * (0.5 - fabs((double)(r / (float)im.h) - 0.5)));
 			s0 += col[0] * w; s1 += col[1] * w; s2 += col[2] * w;
@@ -435,6 +458,103 @@ __global__ void __launch_bounds__(256) k_gain_block_overlap(BlendGeom g, BlendTr
 	}
 }
 
+// ---- vignetting statistics for op_vignette_overlap: k_gain_overlap's lattice, cover walk and sampling, every slot carrying
+// the grey level Y and the radius rho of its sample instead of its colour; a sample whose largest channel exceeds `clip`
+// does not take part (saturated).  For every pair (a < b) of valid samples, with pa[k] = rho_a^k, pb[k] = rho_b^k
+// (fp64, pa[0] = 1, pa[k] = pa[k-1] * rho_a):
+//   N += 1,  A_k += (Ya Ya) pb[k],  B_k += (Yb Yb) pa[k]  (k = 0..6),  C_ij += ((Ya Yb) pa[i]) pb[j]  (i, j = 0..3),
+// each product in fp64 in that order from the fp32 Y / rho, summed as llrint(x 2^32) in int64.  Every term lies in [0, 1]
+// (clip <= 1, rho clamped to [0, 1]) and the host caps the lattice at 2^30 points, so no sum can overflow.  Moment m of pair
+// p at moments[30 p + m]: A_k at m = k, B_k at 7 + k, C_ij at 14 + 4 i + j.  A wavefront reduces the 30 moments one at a
+// time (butterfly: every lane ends with the sum) and lane m keeps moment m; lane 30 the count -- then ONE atomic instruction
+// of 31 lanes per pair instead of 31 from lane 0.
+constexpr int VIG_MOMENTS = 30;
+constexpr long long VIG_MAX_LATTICE = 1ll << 30;           // lattice points per call: bounds every pair's sums (see above)
+__device__ __forceinline__ void vignette_pair(int a, int b, int n, bool va, float ya, float ra, bool vb, float yb, float rb,
+		unsigned long long* __restrict__ count, unsigned long long* __restrict__ moments) {
+	const bool both = va && vb;
+	const unsigned long long bal = __ballot(both);
+	if (!bal) return;                                   // wave-uniform
+	const int lane = threadIdx.x & 63;
+	const double Ya = (double)ya, Yb = (double)yb, Ra = (double)ra, Rb = (double)rb;
+	const double aa = Ya * Ya, bb = Yb * Yb, ab = Ya * Yb;
+	long long mine = (long long)__popcll(bal);           // lane 30's value; lanes 0..29 replace it with their moment
+	// one moment per trip, x = (base pa[i]) pb[j]: A_k = (aa 1) pb[k], B_k = (bb pa[k]) 1 -- the products stated above,
+	// since multiplying by 1.0 is exact.  Kept a loop (uniform trip counts, no arrays): 28 + 8 inlined pairs per chunk.
+#pragma unroll 1
+	for (int m = 0; m < VIG_MOMENTS; ++m) {
+		const int pi = m < 7 ? 0 : (m < 14 ? m - 7 : (m - 14) >> 2), pj = m < 7 ? m : (m < 14 ? 0 : (m - 14) & 3);
+		const double base = m < 7 ? aa : (m < 14 ? bb : ab);
+		double pa = 1.0, pb = 1.0;
+		for (int q = 0; q < pi; ++q) pa *= Ra;
+		for (int q = 0; q < pj; ++q) pb *= Rb;
+		const double x = (base * pa) * pb;
+		const long long s = wave_sum(both ? llrint(x * GAIN_FIX) : 0);
+		if (lane == m) mine = s;
+	}
+	if (lane <= VIG_MOMENTS) {
+		const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+		atomicAdd(lane < VIG_MOMENTS ? moments + (long long)VIG_MOMENTS * p + lane : count + p, (unsigned long long)mine);
+	}
+}
+__global__ void __launch_bounds__(256) k_vignette_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
+		int H, int W, int stride, int lazy, float clip, unsigned long long* __restrict__ count, unsigned long long* __restrict__ moments) {
+	extern __shared__ unsigned long long s_gcover[];
+	const int words = (n + 63) >> 6;
+	const int i = (blockIdx.y * 4 + (threadIdx.x >> 6)) * stride;
+	const int j = (blockIdx.x * 64 + (threadIdx.x & 63)) * stride;
+	const bool live = i < H && j < W;
+	{	// tile_cover over all n images at once (as k_gain_overlap)
+		const int i0 = blockIdx.y * 4 * stride, j0 = blockIdx.x * 64 * stride, excl = lazy ? 1 : 0;
+		for (int k = (int)threadIdx.x; k < words * 64; k += 256) {
+			bool hit = false;
+			if (k < n) {
+				const BlendImg& im = imgs[k];
+				hit = im.x0 <= j0 + 63 * stride && im.x1 - excl >= j0 && im.y0 <= i0 + 3 * stride && im.y1 - excl >= i0;
+			}
+			const unsigned long long b = __ballot(hit);
+			if ((threadIdx.x & 63) == 0) s_gcover[k >> 6] = b;
+		}
+		__syncthreads();
+	}
+	double hx, hy, hz;
+	proj2homo(g, trig, i, j, hx, hy, hz);
+	auto sample = [&](int k, float& y, float& rho) -> bool {
+		float r, c, col[3];
+		y = 0.f; rho = 0.f;
+		const BlendImg& im = imgs[k];
+		if (!(live && linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col))) return false;
+		if (fmaxf(col[0], fmaxf(col[1], col[2])) > clip) return false;
+		y = vignette_grey(col);
+		rho = vignette_rho(r, c, im.w, im.h);
+		return true;
+	};
+	int a0 = next_cover(s_gcover, words, 0);
+	while (a0 < n) {
+		int ka[GAIN_CH]; bool va[GAIN_CH]; float ya[GAIN_CH], ra[GAIN_CH];
+		int k = a0;
+#pragma unroll
+		for (int s = 0; s < GAIN_CH; ++s) {
+			ka[s] = k;
+			va[s] = false; ya[s] = 0.f; ra[s] = 0.f;
+			if (k < n) { va[s] = sample(k, ya[s], ra[s]); k = next_cover(s_gcover, words, k + 1); }
+		}
+#pragma unroll
+		for (int s = 0; s < GAIN_CH; ++s)
+#pragma unroll
+			for (int t = s + 1; t < GAIN_CH; ++t)
+				if (ka[t] < n) vignette_pair(ka[s], ka[t], n, va[s], ya[s], ra[s], va[t], ya[t], ra[t], count, moments);
+		const int a1 = k;                               // first covered image after this chunk
+		for (int b = a1; b < n; b = next_cover(s_gcover, words, b + 1)) {
+			float yb, rb;
+			const bool vb = sample(b, yb, rb);
+#pragma unroll
+			for (int s = 0; s < GAIN_CH; ++s) vignette_pair(ka[s], b, n, va[s], ya[s], ra[s], vb, yb, rb, count, moments);
+		}
+		a0 = a1;
+	}
+}
+
 // ---- create_first_level + update_weight_map (multiband.cc:19-56,125-143) in ONE pass, thread per canvas pixel:
 // proj2homo once per pixel (it does not depend on the image), then every image whose ROI covers the pixel in index
 // order: its level-0 WeightedPixel is written with weight 0 while the winner of the winner-takes-all map -- the first
@@ -443,7 +563,8 @@ __global__ void __launch_bounds__(256) k_gain_block_overlap(BlendGeom g, BlendTr
 // (the two-kernel form re-read every weight and rewrote it: 0.49 GB of the 1.33 GB the two kernels moved), and the
 // target canvas / its "seen" mask are initialised here too (fill(target, Color::NO), multiband.cc:60-61).
 // GM (as k_blend_linear's): the level-0 colours are the gained samples (op_blend_gains, op_blend_block_gains -- the block
-// gain interpolated at the floats interpolate() reads); the weights do not depend on colour.
+// gain interpolated at the floats interpolate() reads; op_blend_vignette -- the curve at those floats); the weights do not
+// depend on colour.
 template <int GM>
 __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		float4* __restrict__ cur, unsigned char* __restrict__ mask, float* __restrict__ out, unsigned char* __restrict__ tmask, int H, int W,
@@ -474,6 +595,7 @@ __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig t
 			if (ok) { float mn = fminf(col[0], fminf(col[1], col[2])); if (mn < 0) ok = false; }
 			if (GM == GAIN_IMAGE && ok) apply_gain(gains + 3 * (long long)k, col);
 			if (GM == GAIN_BLOCK && ok) apply_block_gain(gains + 3 * (long long)k * gbx * gby, gbx, gby, im.w, im.h, (float)oy, (float)ox, col);
+			if (GM == GAIN_VIGNETTE && ok) apply_vignette(gains + 3 * (long long)k, gains + 3 * (long long)n, im.w, im.h, (float)oy, (float)ox, col);
 			float4 px = make_float4(0.f, 0.f, 0.f, 0.f);
 			if (ok) {
 				const double x = ox / (double)im.w - 0.5, y = oy / (double)im.h - 0.5;
@@ -1123,10 +1245,10 @@ int check_blend_args(const char* who, const op_blend_geom* g) {
 	return OP_OK;
 }
 
-// op_blend (gains == NULL), op_blend_gains (gbx == 0, gains: n x 3 on the host) and op_blend_block_gains (gbx, gby >= 1,
-// gains: n x gby x gbx x 3 on the host)
+// op_blend (gains == NULL), op_blend_gains (gbx == 0, gains: n x 3 on the host), op_blend_block_gains (gbx, gby >= 1,
+// gains: n x gby x gbx x 3 on the host) and op_blend_vignette (vignette: n x 3 gains then a1..a3, 3 n + 3 host floats)
 int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
-		int gbx, int gby, const char* who, op_canvas** out) {
+		int gbx, int gby, const char* who, op_canvas** out, const float* vignette = nullptr) {
 	int rc = check_blend_args(who, g);
 	if (rc != OP_OK) return rc;
 	HIPCHK(hipSetDevice(ctx->device));
@@ -1142,9 +1264,10 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	rc = upload_images(ctx, who, g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
 	if (rc != OP_OK) return rc;
 	float* d_gains = nullptr;
-	const int gm = !gains ? GAIN_NONE : (gbx > 0 ? GAIN_BLOCK : GAIN_IMAGE);
+	const int gm = vignette ? GAIN_VIGNETTE : (!gains ? GAIN_NONE : (gbx > 0 ? GAIN_BLOCK : GAIN_IMAGE));
+	if (vignette) gains = vignette;
 	if (gains) {                 // the whole table, once per call
-		const size_t ng = 3 * (size_t)n * (gm == GAIN_BLOCK ? (size_t)gbx * gby : 1);
+		const size_t ng = gm == GAIN_VIGNETTE ? 3 * (size_t)n + 3 : 3 * (size_t)n * (gm == GAIN_BLOCK ? (size_t)gbx * gby : 1);
 		HIPCHK(pool_alloc((void**)&d_gains, sizeof(float) * ng)); fr.v.push_back(d_gains);
 		HIPCHK(hipMemcpyAsync(d_gains, gains, sizeof(float) * ng, hipMemcpyHostToDevice, st));
 	}
@@ -1163,7 +1286,8 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	pool_free(cv->data); delete cv; return OP_ERR_HIP; } } while (0)
 	if (cfg->MULTIBAND <= 0) {
 		ProfScope ps(ctx, "blend linear");
-		if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_blend_linear<GAIN_BLOCK>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
+		if (gm == GAIN_VIGNETTE) hipLaunchKernelGGL(k_blend_linear<GAIN_VIGNETTE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, 0, 0);
+		else if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_blend_linear<GAIN_BLOCK>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
 		else if (gm == GAIN_IMAGE) hipLaunchKernelGGL(k_blend_linear<GAIN_IMAGE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, 0, 0);
 		else hipLaunchKernelGGL(k_blend_linear<GAIN_NONE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, nullptr, 0, 0);
 		BCHK(hipGetLastError());
@@ -1182,7 +1306,8 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 		const dim3 rgrid((unsigned)((max_roi + 255) / 256), n);
 		{ ProfScope ps(ctx, "multiband first level");
 		  const dim3 fgrid((W + 1 + 63) / 64, (H + 1 + 3) / 4);
-		  if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_mb_first_fused<GAIN_BLOCK>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, gbx, gby);
+		  if (gm == GAIN_VIGNETTE) hipLaunchKernelGGL(k_mb_first_fused<GAIN_VIGNETTE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, 0, 0);
+		  else if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_mb_first_fused<GAIN_BLOCK>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, gbx, gby);
 		  else if (gm == GAIN_IMAGE) hipLaunchKernelGGL(k_mb_first_fused<GAIN_IMAGE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, 0, 0);
 		  else hipLaunchKernelGGL(k_mb_first_fused<GAIN_NONE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, nullptr, 0, 0);
 		  BCHK(hipGetLastError()); }
@@ -1241,6 +1366,31 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	return OP_OK;
 }
 
+// The vignetting curve V(rho) = 1 + a1 rho + a2 rho^2 + a3 rho^3 (a: a1..a3) stays above VIG_MIN_CURVE on [0, 1]: its minimum
+// there lies at rho = 0 (V = 1), rho = 1 or a root of V' inside, all checked in fp64.
+constexpr double VIG_MIN_CURVE = 1e-6;
+bool vignette_curve_positive(const double a[3]) {
+	if (!std::isfinite(a[0]) || !std::isfinite(a[1]) || !std::isfinite(a[2])) return false;
+	auto V = [&](double r) { return 1.0 + r * (a[0] + r * (a[1] + r * a[2])); };
+	double cand[3] = {1.0, -1.0, -1.0};
+	if (a[2] != 0.0) {                                  // V' = a1 + 2 a2 rho + 3 a3 rho^2
+		const double disc = 4.0 * a[1] * a[1] - 12.0 * a[2] * a[0];
+		if (disc >= 0.0) { const double sq = std::sqrt(disc); cand[1] = (-2.0 * a[1] + sq) / (6.0 * a[2]); cand[2] = (-2.0 * a[1] - sq) / (6.0 * a[2]); }
+	} else if (a[1] != 0.0) cand[1] = -a[0] / (2.0 * a[1]);
+	for (double r : cand)
+		if (r >= 0.0 && r <= 1.0 && !(V(r) > VIG_MIN_CURVE)) return false;
+	return true;
+}
+
+// the views of the vignetting entry points are in their own lens frame: a cylinder pre-warp -- a pixel buffer whose size
+// (mat_h / mat_w, when set) differs from the ImageRef's -- is refused
+int check_lens_frame(const char* who, const op_blend_image* imgs, int n) {
+	for (int k = 0; k < n; ++k)
+		if ((imgs[k].mat_h > 0 && imgs[k].mat_h != imgs[k].h) || (imgs[k].mat_w > 0 && imgs[k].mat_w != imgs[k].w))
+			OP_FAIL(OP_ERR_UNSUPPORTED, std::string(who) + ": image " + std::to_string(k) + " is pre-warped (mat_h / mat_w set): its samples are not in the lens frame");
+	return OP_OK;
+}
+
 }	// namespace
 
 extern "C" {
@@ -1268,6 +1418,73 @@ int op_blend_block_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom*
 			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
 				OP_FAIL(OP_ERR_INVALID, "op_blend_block_gains: gain " + std::to_string(e) + " (image " + std::to_string(e / (3 * bx * by)) + ") is not finite and positive");
 	return blend_impl(ctx, cfg, g, imgs, n, gains, bx, by, "op_blend_block_gains", out);
+}
+
+int op_blend_vignette(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
+		const float* poly, op_canvas** out) {
+	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend_vignette: bad argument");
+	int rc = check_lens_frame("op_blend_vignette", imgs, n);
+	if (rc != OP_OK) return rc;
+	std::vector<float> table(3 * (size_t)n + 3, 1.f);   // gains (NULL = 1), then a1..a3 (NULL = 0)
+	if (gains)
+		for (int e = 0; e < 3 * n; ++e) {
+			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
+				OP_FAIL(OP_ERR_INVALID, "op_blend_vignette: gain " + std::to_string(e) + " (image " + std::to_string(e / 3) + ") is not finite and positive");
+			table[e] = gains[e];
+		}
+	for (int j = 0; j < 3; ++j) table[3 * (size_t)n + j] = poly ? poly[j] : 0.f;
+	const double a[3] = {table[3 * (size_t)n], table[3 * (size_t)n + 1], table[3 * (size_t)n + 2]};
+	if (!vignette_curve_positive(a)) OP_FAIL(OP_ERR_INVALID, "op_blend_vignette: the curve is not finite and positive on [0, 1]");
+	return blend_impl(ctx, cfg, g, imgs, n, nullptr, 0, 0, "op_blend_vignette", out, table.data());
+}
+
+int op_vignette_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
+		float clip, int64_t* count, int64_t* moments) {
+	if (!ctx || !cfg || !g || !imgs || n < 1 || stride < 1 || !(clip > 0.f) || !(clip <= 1.f) || (n > 1 && (!count || !moments)))
+		OP_FAIL(OP_ERR_INVALID, "op_vignette_overlap: bad argument");
+	int rc = check_blend_args("op_vignette_overlap", g);
+	if (rc != OP_OK) return rc;
+	rc = check_lens_frame("op_vignette_overlap", imgs, n);
+	if (rc != OP_OK) return rc;
+	const int words = (n + 63) / 64;
+	if (words > GAIN_MAX_IMAGES / 64) OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
+	const long long npairs = (long long)n * (n - 1) / 2;
+	if (npairs == 0) return OP_OK;
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	int H, W;
+	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
+	if (rc != OP_OK) return rc;
+	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, "op_vignette_overlap: empty canvas");
+	stride = std::min(stride, std::max(H, W));
+	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
+	if ((long long)hs_ * ws_ > VIG_MAX_LATTICE)
+		OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_overlap: " + std::to_string((long long)hs_ * ws_) + " lattice points exceed 2^30 (raise the stride)");
+	Freer fr;
+	std::vector<BlendImg> h_imgs;
+	long long roi_total = 0, max_roi = 0;
+	BlendImg* d_imgs = nullptr;
+	rc = upload_images(ctx, "op_vignette_overlap", g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
+	if (rc != OP_OK) return rc;
+	unsigned long long* d_stats = nullptr;         // npairs counts, then npairs x 30 moments
+	const size_t stat_bytes = sizeof(unsigned long long) * (1 + VIG_MOMENTS) * (size_t)npairs;
+	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
+	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
+	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
+	BlendTrig trig{nullptr, nullptr, 0, 0};
+	if (bg.method != 0) {
+		HostScope hs(ctx, "blend trig tables (host)");
+		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
+	}
+	{ ProfScope ps(ctx, "vignette overlap");
+	  hipLaunchKernelGGL(k_vignette_overlap, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * words, st,
+	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, clip, d_stats, d_stats + npairs);
+	  HIPCHK(hipGetLastError()); }
+	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)npairs, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(moments, d_stats + npairs, sizeof(int64_t) * VIG_MOMENTS * (size_t)npairs, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	resolve_profile(ctx);
+	return OP_OK;
 }
 
 int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
@@ -1536,6 +1753,125 @@ int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64
 				else o[0] = o[1] = o[2] = gv;
 			}
 	}
+	return OP_OK;
+}
+
+// Vignetting compensation, host only: gains g_k and one curve a = (1, a1, a2, a3) shared by all views minimising
+//   E = sum_p [ (g_a^2 a'H(A)a - 2 g_a g_b a'Ca + g_b^2 a'H(B)a) / sigma_n^2 + N ((1 - g_a)^2 + (1 - g_b)^2) / sigma_g^2 ]
+//     + (sum_p N) (a1^2 + a2^2 + a3^2) / sigma_v^2,
+// the first term the sum over the pair's samples of (g_a Y_a V(rho_b) - g_b Y_b V(rho_a))^2 written with the moments
+// (H(A) the Hankel matrix A_{i+j}, moments / 2^32).  Alternation from a = 0, each step a closed-form SPD solve: g given a
+// (op_gain_solve's pattern, its Cholesky), then a1..a_degree given g (degree x degree); stop after VIG_MAX_ROUNDS rounds or
+// when a round lowers E by no more than VIG_TOL E; then the gains are normalised to an overlap-weighted mean of 1.  fp64,
+// fixed order: a function of the statistics alone.
+constexpr int VIG_MAX_ROUNDS = 100;
+constexpr double VIG_TOL = 1e-12;
+int op_vignette_solve(int n, const int64_t* count, const int64_t* moments, int degree, double sigma_n, double sigma_g, double sigma_v,
+		float* gains, float* poly) {
+	if (n < 1 || !gains || !poly || (n > 1 && (!count || !moments)) || degree < 1 || degree > 3 || !(sigma_n > 0) || !(sigma_g > 0) ||
+			!(sigma_v > 0) || !std::isfinite(sigma_n) || !std::isfinite(sigma_g) || !std::isfinite(sigma_v))
+		OP_FAIL(OP_ERR_INVALID, "op_vignette_solve: bad argument");
+	const long long npairs = (long long)n * (n - 1) / 2;
+	for (long long p = 0; p < npairs; ++p)
+		if (count[p] < 0) OP_FAIL(OP_ERR_INVALID, "op_vignette_solve: negative overlap count at pair " + std::to_string(p));
+	for (int e = 0; e < 3 * n; ++e) gains[e] = 1.f;
+	poly[0] = poly[1] = poly[2] = 0.f;
+	// the pairs with overlap, in pair order, with their moments in [0, 1] units; the active images as op_gain_solve's
+	struct VPair { int a, b; double N, A[7], B[7], C[16]; };
+	std::vector<VPair> pairs;
+	std::vector<int> slot(n, -1), act;
+	double Mtot = 0.0;
+	for (int a = 0; a < n; ++a)
+		for (int b = a + 1; b < n; ++b) {
+			const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+			if (count[p] <= 0) continue;
+			VPair v; v.a = a; v.b = b; v.N = (double)count[p];
+			const int64_t* m = moments + (long long)VIG_MOMENTS * p;
+			for (int k = 0; k < 7; ++k) { v.A[k] = (double)m[k] / GAIN_FIX; v.B[k] = (double)m[7 + k] / GAIN_FIX; }
+			for (int k = 0; k < 16; ++k) v.C[k] = (double)m[14 + k] / GAIN_FIX;
+			pairs.push_back(v);
+			slot[a] = slot[b] = 0;
+			Mtot += v.N;
+		}
+	for (int a = 0; a < n; ++a) if (slot[a] == 0) { slot[a] = (int)act.size(); act.push_back(a); }
+	const int m = (int)act.size();
+	if (m == 0) return OP_OK;
+	const double inv_n2 = 1.0 / (sigma_n * sigma_n), inv_g2 = 1.0 / (sigma_g * sigma_g), inv_v2 = 1.0 / (sigma_v * sigma_v);
+	double a[4] = {1.0, 0.0, 0.0, 0.0};
+	std::vector<double> g(n, 1.0);
+	// a'Ma for the Hankel matrix of h, and for C (row: the power of rho_a)
+	auto hank = [&](const double* h) { double t = 0.0; for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) t += a[i] * a[j] * h[i + j]; return t; };
+	auto cross = [&](const double* c) { double t = 0.0; for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) t += a[i] * a[j] * c[4 * i + j]; return t; };
+	auto energy = [&]() {
+		double e = 0.0;
+		for (const VPair& v : pairs) {
+			const double ga = g[v.a], gb = g[v.b];
+			e += (ga * ga * hank(v.A) - 2.0 * ga * gb * cross(v.C) + gb * gb * hank(v.B)) * inv_n2;
+			e += v.N * ((1.0 - ga) * (1.0 - ga) + (1.0 - gb) * (1.0 - gb)) * inv_g2;
+		}
+		return e + Mtot * (a[1] * a[1] + a[2] * a[2] + a[3] * a[3]) * inv_v2;
+	};
+	std::vector<double> A((size_t)m * m), rhs(m);
+	double e_prev = energy();
+	for (int round = 0; round < VIG_MAX_ROUNDS; ++round) {
+		// g given a
+		std::fill(A.begin(), A.end(), 0.0); std::fill(rhs.begin(), rhs.end(), 0.0);
+		for (const VPair& v : pairs) {
+			const int sa = slot[v.a], sb = slot[v.b];
+			A[(size_t)sa * m + sa] += hank(v.A) * inv_n2 + v.N * inv_g2;
+			A[(size_t)sb * m + sb] += hank(v.B) * inv_n2 + v.N * inv_g2;
+			const double off = cross(v.C) * inv_n2;
+			A[(size_t)sa * m + sb] -= off;
+			A[(size_t)sb * m + sa] -= off;
+			rhs[sa] += v.N * inv_g2;
+			rhs[sb] += v.N * inv_g2;
+		}
+		if (!gain_cholesky_solve(A, rhs, m)) OP_FAIL(OP_ERR_INVALID, "op_vignette_solve: gain system not positive definite (inconsistent statistics)");
+		for (int i = 0; i < m; ++i) g[act[i]] = rhs[i];
+		// a given g: Q = sum_p [g_a^2 H(A) - g_a g_b (C + C') + g_b^2 H(B)] / sigma_n^2, then
+		// (Q[1.., 1..] + (sum N) / sigma_v^2 I) a' = -Q[1.., 0]
+		double Q[16] = {0};
+		for (const VPair& v : pairs) {
+			const double ga = g[v.a], gb = g[v.b];
+			for (int i = 0; i < 4; ++i)
+				for (int j = 0; j < 4; ++j)
+					Q[4 * i + j] += (ga * ga * v.A[i + j] - ga * gb * (v.C[4 * i + j] + v.C[4 * j + i]) + gb * gb * v.B[i + j]) * inv_n2;
+		}
+		std::vector<double> S((size_t)degree * degree), r(degree);
+		for (int i = 0; i < degree; ++i) {
+			for (int j = 0; j < degree; ++j) S[(size_t)i * degree + j] = Q[4 * (i + 1) + (j + 1)] + (i == j ? Mtot * inv_v2 : 0.0);
+			r[i] = -Q[4 * (i + 1)];
+		}
+		if (!gain_cholesky_solve(S, r, degree)) OP_FAIL(OP_ERR_INVALID, "op_vignette_solve: curve system not positive definite (inconsistent statistics)");
+		for (int i = 0; i < degree; ++i) a[1 + i] = r[i];
+		const double e = energy();
+		const bool done = !(e_prev - e > VIG_TOL * e_prev);
+		e_prev = e;
+		if (done) break;
+	}
+	// The data term fixes the gains' common scale only where the model fits; where overlaps disagree it pulls every gain
+	// towards 0, and sigma_g = 1 resists weakly (misregistered overlaps: gains of 0.26).  The panorama keeps
+	// its brightness: the gains are divided by their overlap-weighted mean s = sum_p N_p (g_a + g_b) / (2 sum_p N_p) --
+	// ratios and curve unchanged, and s ~ 1 wherever the model fits (the prior then sets the scale to about that).
+	double ssum = 0.0;
+	for (const VPair& v : pairs) ssum += v.N * (g[v.a] + g[v.b]);
+	const double s = ssum / (2.0 * Mtot);
+	if (s > 0.0)
+		for (int i = 0; i < m; ++i) g[act[i]] /= s;
+	float pf[3] = {0.f, 0.f, 0.f};
+	for (int i = 0; i < degree; ++i) pf[i] = (float)a[1 + i];
+	const double ad[3] = {pf[0], pf[1], pf[2]};
+	bool gains_ok = true;
+	for (int i = 0; i < m; ++i) gains_ok = gains_ok && std::isfinite((float)g[act[i]]) && (float)g[act[i]] > 0.f;
+	if (!gains_ok) OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_solve: a fitted gain is not finite and positive: keep plain gains");
+	if (!vignette_curve_positive(ad))
+		OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_solve: the fitted curve is not positive on [0, 1] (a = " + std::to_string(pf[0]) + ", " +
+		        std::to_string(pf[1]) + ", " + std::to_string(pf[2]) + "): keep plain gains");
+	for (int i = 0; i < m; ++i) {
+		const float gv = (float)g[act[i]];
+		gains[3 * act[i]] = gains[3 * act[i] + 1] = gains[3 * act[i] + 2] = gv;
+	}
+	for (int i = 0; i < 3; ++i) poly[i] = pf[i];
 	return OP_OK;
 }
 

@@ -211,6 +211,13 @@ def lib():
                                           C.c_int, C.c_void_p]
         L.op_blend_block_gains.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
                                            C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+    if hasattr(L, "op_vignette_overlap"):
+        L.op_vignette_overlap.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
+                                          C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        L.op_vignette_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                        C.c_void_p]
+        L.op_blend_vignette.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
+                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
@@ -795,6 +802,9 @@ GAIN_FIX = 2.0 ** 32                  # fixed-point scale of op_gain_overlap's c
 GAIN_SIGMA_N, GAIN_SIGMA_G = 10.0 / 255.0, 0.1
 GAIN_SIGMA_S = 0.1                    # smoothness of block gains (op_gain_block_solve)
 GAIN_BLOCK_MAX_ENTRIES = 1 << 22      # op_gain_block_overlap's cap on pairs x (bx by)^2 (include/openpano_hip.h)
+VIG_SIGMA_N, VIG_SIGMA_G, VIG_SIGMA_V = 10.0 / 255.0, 1.0, 100.0   # op_vignette_solve's usual priors
+VIG_STRIDE, VIG_CLIP = 2, 0.98        # op_vignette_overlap's usual lattice stride and saturation clip
+VIG_MOMENTS = 30                      # moments per pair: A_0..6, B_0..6, C_00..33
 
 
 def _gains_array(gains, n):
@@ -816,10 +826,11 @@ def _gains_array(gains, n):
 class BlendCall:
     """``ConnectedImages::blend()`` (stitcher_image.cc:116-155) with the op_blend_geom / op_blend_image arrays marshalled
     once, like a C host holds them; every call is one op_blend -- or, with ``gains`` ((n, 3) or (n,) exposure gains), one
-    op_blend_gains; with (n, by, bx, 3) block gains, one op_blend_block_gains.
+    op_blend_gains; with (n, by, bx, 3) block gains, one op_blend_block_gains; with ``vignette`` (a1, a2, a3: the shared
+    curve of op_vignette_solve), one op_blend_vignette of ``gains`` ((n, 3), (n,) or None = 1).
     images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo."""
 
-    def __init__(self, ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None):
+    def __init__(self, ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None, vignette=None):
         self.ctx = ctx
         n = self.n = len(images)
         arr_img, self._keep = _mk_images(images)
@@ -834,11 +845,22 @@ class BlendCall:
                 arr[i].range[k] = ranges[i, k]
         self.ccfg = OpConfig.from_config(cfg)
         self.gains = _gains_array(gains, n)
+        self.vignette = None
+        if vignette is not None:
+            self.vignette = np.ascontiguousarray(np.asarray(vignette, np.float32).reshape(-1))
+            if self.vignette.shape != (3,):
+                raise ValueError(f"vignette must hold the 3 coefficients a1, a2, a3, got {self.vignette.shape}")
+            if self.gains is not None and self.gains.ndim != 2:
+                raise ValueError("vignetting takes per-image gains (n, 3), not block gains")
         self._fn = lib().op_blend
 
     def __call__(self) -> Canvas:
         h = C.c_void_p()
-        if self.gains is None:
+        if self.vignette is not None:
+            check(lib().op_blend_vignette(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n,
+                                          None if self.gains is None else self.gains.ctypes.data_as(C.c_void_p),
+                                          self.vignette.ctypes.data_as(C.c_void_p), C.byref(h)))
+        elif self.gains is None:
             check(self._fn(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, C.byref(h)))
         elif self.gains.ndim == 4:
             by, bx = self.gains.shape[1:3]
@@ -858,6 +880,16 @@ class BlendCall:
                                     count.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
         return count[:npairs], sums[:npairs]
 
+    def vignette_overlap_sums(self, stride=VIG_STRIDE, clip=VIG_CLIP):
+        """op_vignette_overlap over this call's canvas -> (count (P,) int64, moments (P, 30) int64 in units of 2^-32):
+        A_k = sum Ya^2 rho_b^k at [p, k], B_k = sum Yb^2 rho_a^k at [p, 7 + k] (k = 0..6), C_ij = sum Ya Yb rho_a^i rho_b^j
+        at [p, 14 + 4 i + j] (i, j = 0..3); samples whose largest channel exceeds clip are left out."""
+        npairs = self.n * (self.n - 1) // 2
+        count = np.zeros(max(npairs, 1), np.int64); mom = np.zeros((max(npairs, 1), VIG_MOMENTS), np.int64)
+        check(lib().op_vignette_overlap(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(stride),
+                                        float(clip), count.ctypes.data_as(C.c_void_p), mom.ctypes.data_as(C.c_void_p)))
+        return count[:npairs], mom[:npairs]
+
     def block_overlap_sums(self, bx, by, stride=1):
         """op_gain_block_overlap -> (count (P, B, B) int64, sums (P, B, B, 6) int64 fixed point), B = bx * by: the entry
         [p, qa, qb] holds the samples of pair p = pair_index(n, a, b) whose a-side lies in block qa = v * bx + u of image a
@@ -872,12 +904,12 @@ class BlendCall:
         return count[:npairs], sums[:npairs]
 
 
-def blend(ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None) -> Canvas:
+def blend(ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None, vignette=None) -> Canvas:
     """``ConnectedImages::blend()`` (stitcher_image.cc:116-155) on the device.
     images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo.
     gains: optional (n, 3) or (n,) exposure gains (op_blend_gains), or (n, by, bx, 3) block gains (op_blend_block_gains);
-    None = op_blend."""
-    return BlendCall(ctx, cfg, images, homos, proj_method, identity_idx, gains=gains)()
+    None = op_blend.  vignette: optional (a1, a2, a3), the shared curve of vignette_solve (op_blend_vignette, with gains)."""
+    return BlendCall(ctx, cfg, images, homos, proj_method, identity_idx, gains=gains, vignette=vignette)()
 
 
 def pair_index(n, a, b):
@@ -939,6 +971,30 @@ def gain_block_compensate(ctx: Context, cfg, images, homos, proj_method, identit
     call = BlendCall(ctx, cfg, images, homos, proj_method, identity_idx)
     count, sums = call.block_overlap_sums(bx, by, stride)
     return gain_block_solve(len(images), bx, by, count, sums, sigma_n, sigma_g, sigma_s, per_channel)
+
+
+def vignette_solve(n, count, moments, degree=3, sigma_n=VIG_SIGMA_N, sigma_g=VIG_SIGMA_G, sigma_v=VIG_SIGMA_V):
+    """op_vignette_solve (host only): (gains (n, 3) float32, poly (3,) float32 = a1, a2, a3) from op_vignette_overlap's
+    count / moments.  Raises OpenPanoHipError (code OP_ERR_UNSUPPORTED) when the fitted curve is not positive on [0, 1]:
+    fall back to gain_solve then."""
+    npairs = n * (n - 1) // 2
+    c = np.ascontiguousarray(np.asarray(count, np.int64).reshape(-1))
+    m = np.ascontiguousarray(np.asarray(moments, np.int64).reshape(-1, VIG_MOMENTS))
+    if len(c) != npairs or len(m) != npairs:
+        raise ValueError(f"{n} images need {npairs} pairs, got {len(c)} counts and {len(m)} moment rows")
+    gains = np.zeros((n, 3), np.float32); poly = np.zeros(3, np.float32)
+    check(lib().op_vignette_solve(int(n), c.ctypes.data_as(C.c_void_p) if npairs else None, m.ctypes.data_as(C.c_void_p) if npairs else None,
+                                  int(degree), float(sigma_n), float(sigma_g), float(sigma_v), gains.ctypes.data_as(C.c_void_p),
+                                  poly.ctypes.data_as(C.c_void_p)))
+    return gains, poly
+
+
+def vignette_compensate(ctx: Context, cfg, images, homos, proj_method, identity_idx, stride=VIG_STRIDE, clip=VIG_CLIP, degree=3,
+                        sigma_n=VIG_SIGMA_N, sigma_g=VIG_SIGMA_G, sigma_v=VIG_SIGMA_V):
+    """op_vignette_overlap + op_vignette_solve: (gains (n, 3), poly (3,)) to pass to blend(..., gains=gains, vignette=poly)"""
+    call = BlendCall(ctx, cfg, images, homos, proj_method, identity_idx)
+    count, moments = call.vignette_overlap_sums(stride, clip)
+    return vignette_solve(len(images), count, moments, degree, sigma_n, sigma_g, sigma_v)
 
 
 def cyl_warp_shape(cfg, w, h, h_factor, pts=None):

@@ -23,6 +23,7 @@
 // (lib/debugutils.cc:57-60: message on stderr, exit(1)); no exception crosses the C-ABI.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -660,10 +661,36 @@ inline std::vector<float> hip_gain_compensate_blocks(const Bundle& b, int bx, in
 	return gains;
 }
 
+// Vignetting compensation (the C-ABI's op_vignette_overlap + op_vignette_solve): n x 3 grey exposure gains (returned) and
+// one radial falloff curve V(rho) = 1 + a1 rho + a2 rho^2 + a3 rho^3 shared by all views (poly = a1, a2, a3); pass both to
+// hip_blend(b, crop, gains, poly).  When the fitted curve is not positive on [0, 1] (the solve's OP_ERR_UNSUPPORTED) this
+// keeps plain gains: hip_gain_compensate's, with poly = 0.
+template <typename Bundle>
+inline std::vector<float> hip_vignette_compensate(const Bundle& b, std::array<float, 3>& poly, int stride = 2, float clip = 0.98f,
+		int degree = 3, double sigma_n = 10.0 / 255.0, double sigma_g = 1.0, double sigma_v = 100.0) {
+	op_ctx* ctx = HipContext::get();
+	const op_config cfg = hip_config_snapshot();
+	const int n = (int)b.component.size();
+	op_blend_geom g;
+	const std::vector<op_blend_image> ims = hip_blend_images(b, g);
+	const size_t npairs = (size_t)n * (n - 1) / 2;
+	std::vector<int64_t> count(npairs + 1), moments(30 * npairs + 1);
+	std::vector<float> gains((size_t)3 * n);
+	PANO_HIP_CHECK(op_vignette_overlap(ctx, &cfg, &g, ims.data(), n, stride, clip, count.data(), moments.data()));
+	const int rc = op_vignette_solve(n, count.data(), moments.data(), degree, sigma_n, sigma_g, sigma_v, gains.data(), poly.data());
+	if (rc == OP_ERR_UNSUPPORTED) {
+		fprintf(stderr, "hip_vignette_compensate: %s\n", op_last_error());
+		poly = {0.f, 0.f, 0.f};
+		return hip_gain_compensate(b);
+	}
+	PANO_HIP_CHECK(rc);
+	return gains;
+}
+
 // gains: empty = op_blend; bx = by = 0: n x 3 exposure gains (op_blend_gains); bx, by >= 1: n x by x bx x 3 block gains
 // (op_blend_block_gains)
 template <typename Bundle>
-inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains, int bx, int by) {
+inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains, int bx, int by, const float* poly = nullptr) {
 	op_ctx* ctx = HipContext::get();
 	const op_config cfg = hip_config_snapshot();
 	const int n = (int)b.component.size();
@@ -679,7 +706,8 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 	const size_t per_image = bx > 0 ? (size_t)3 * bx * by : 3;
 	if (!gains.empty() && gains.size() != per_image * n) { fprintf(stderr, "hip_blend: %zu gains for %d images\n", gains.size(), n); exit(1); }
 	op_canvas* cv = nullptr;
-	if (gains.empty()) PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
+	if (poly) PANO_HIP_CHECK(op_blend_vignette(ctx, &cfg, &g, ims.data(), n, gains.empty() ? nullptr : gains.data(), poly, &cv));
+	else if (gains.empty()) PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
 	else if (bx > 0) PANO_HIP_CHECK(op_blend_block_gains(ctx, &cfg, &g, ims.data(), n, bx, by, gains.data(), &cv));
 	else PANO_HIP_CHECK(op_blend_gains(ctx, &cfg, &g, ims.data(), n, gains.data(), &cv));
 	if (crop) {
@@ -699,6 +727,11 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 // gains: empty = op_blend, else n x 3 exposure gains (op_blend_gains)
 template <typename Bundle>
 inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains) { return hip_blend(b, crop, gains, 0, 0); }
+// gains: n x 3 grey exposure gains (empty = 1) under the shared vignetting curve poly = a1, a2, a3 (op_blend_vignette)
+template <typename Bundle>
+inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains, const std::array<float, 3>& poly) {
+	return hip_blend(b, crop, gains, 0, 0, poly.data());
+}
 template <typename Bundle>
 inline Mat32f hip_blend(const Bundle& b, bool crop = false) { return hip_blend(b, crop, std::vector<float>()); }
 
@@ -828,6 +861,12 @@ class HipStitcher {
 			else build_linear_simple();
 			bundle.proj_method = config::ESTIMATE_CAMERA ? ConnectedImages::spherical : ConnectedImages::flat;
 			bundle.update_proj_range();
+			vignette_poly = {0.f, 0.f, 0.f};
+			if (vignetting) {
+				if (gain_blocks_x * gain_blocks_y > 1) { fprintf(stderr, "HipStitcher: vignetting and block gains are exclusive\n"); exit(1); }
+				gains = hip_vignette_compensate(bundle, vignette_poly);   // after the homographies are final
+				return hip_blend(bundle, false, gains, vignette_poly);
+			}
 			if (!gain_compensation) { gains.clear(); return bundle.blend(); }
 			if (gain_blocks_x == 1 && gain_blocks_y == 1) {
 				gains = hip_gain_compensate(bundle);                // after the homographies are final
@@ -849,6 +888,10 @@ class HipStitcher {
 		// that grid on every image (hip_gain_compensate_blocks); `gains` then holds n * by * bx * 3
 		bool gain_compensation = false;
 		int gain_blocks_x = 1, gain_blocks_y = 1;
+		// vignetting: grey gains plus one radial falloff curve shared by all views (hip_vignette_compensate), off by default,
+		// refused together with block gains; `gains` then holds n x 3 and vignette_poly the curve's a1..a3 (0 otherwise)
+		bool vignetting = false;
+		std::array<float, 3> vignette_poly = {0.f, 0.f, 0.f};
 		std::vector<float> gains;
 
 		void calc_feature() {                                       // stitcherbase.cc:9-27

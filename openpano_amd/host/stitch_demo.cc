@@ -18,6 +18,9 @@
 // --gain-blocks BXxBY (anywhere; implies --gain-compensation): block gain compensation on a BX x BY grid per image
 // (HipStitcher::gain_blocks_x / _y, hip_gain_compensate_blocks; 1x1 is --gain-compensation itself); out.bin then ends
 // with n*BY*BX*3 f32 gains, [((k*BY + v)*BX + u)*3 + c], after the canvas (camera modes) or the chain homographies.
+// --vignetting (anywhere; not with --gain-blocks): grey gains plus one radial falloff curve shared by all views
+// (HipStitcher::vignetting, hip_vignette_compensate); out.bin then ends with n*3 f32 gains and the curve's 3 f32
+// coefficients a1, a2, a3, where --gain-compensation puts its gains.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
@@ -77,7 +80,8 @@ static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::
 
 // Stitcher::build() under ESTIMATE_CAMERA (stitch/stitcher.cc:32-64), stage by stage so that every
 // intermediate can be written out
-static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby) {
+static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby,
+		bool vig) {
 	Stitcher st(mats, base_seed);
 	FILE* fo = fopen(out_path, "wb");
 	if (!fo) { perror(out_path); return 2; }
@@ -104,25 +108,32 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 	st.bundle.proj_method = ConnectedImages::spherical;
 	st.bundle.update_proj_range();
 	const bool blocks = gain && gbx * gby > 1;
-	if (blocks) st.gains = hip_gain_compensate_blocks(st.bundle, gbx, gby);   // what HipStitcher::build() does under gain_blocks_x / _y
+	if (vig) st.gains = hip_vignette_compensate(st.bundle, st.vignette_poly);   // what HipStitcher::build() does under vignetting
+	else if (blocks) st.gains = hip_gain_compensate_blocks(st.bundle, gbx, gby);   // what HipStitcher::build() does under gain_blocks_x / _y
 	else if (gain) st.gains = hip_gain_compensate(st.bundle);     // what HipStitcher::build() does under gain_compensation
-	Mat32f pano = blocks ? hip_blend(st.bundle, false, st.gains, gbx, gby) : gain ? hip_blend(st.bundle, false, st.gains) : st.bundle.blend();
+	Mat32f pano = vig ? hip_blend(st.bundle, false, st.gains, st.vignette_poly) : blocks ? hip_blend(st.bundle, false, st.gains, gbx, gby)
+	            : gain ? hip_blend(st.bundle, false, st.gains) : st.bundle.blend();
 	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
-	if (gain) {
+	if (gain || vig) {
 		put(fo, st.gains.data(), st.gains.size());
 		const size_t per = st.gains.size() / n;      // 3 per image, or 3 per block
 		for (int k = 0; k < n; ++k) fprintf(stderr, "gain %d: %g %g %g\n", k, st.gains[per * k], st.gains[per * k + 1], st.gains[per * k + 2]);
+	}
+	if (vig) {
+		put(fo, st.vignette_poly.data(), 3);
+		fprintf(stderr, "vignetting curve: a = %g %g %g\n", st.vignette_poly[0], st.vignette_poly[1], st.vignette_poly[2]);
 	}
 	fclose(fo);
 	return 0;
 }
 
 // Stitcher::build() as a client calls it, gain compensation per HipStitcher::gain_compensation
-static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain, int gbx, int gby) {
+static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain, int gbx, int gby, bool vig) {
 	Stitcher st(mats, base_seed);
 	st.gain_compensation = gain;
+	st.vignetting = vig;
 	st.gain_blocks_x = gbx; st.gain_blocks_y = gby;
 	Mat32f pano = st.build();
 	FILE* fo = fopen(out_path, "wb");
@@ -130,6 +141,7 @@ static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint
 	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 	put(fo, st.gains.data(), st.gains.size());
+	if (vig) put(fo, st.vignette_poly.data(), 3);
 	fclose(fo);
 	fprintf(stderr, "Final Image Size: (%d, %d), %zu gains\n", pano.cols(), pano.rows(), st.gains.size());
 	return 0;
@@ -138,10 +150,12 @@ static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint
 int main(int argc, char** argv) {
 	bool gain = false;
 	int gbx = 1, gby = 1;
+	bool vig = false;
 	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
 			if (std::string(argv[k]) == "--gain-compensation") gain = true;
+			else if (std::string(argv[k]) == "--vignetting") vig = true;
 			else if (std::string(argv[k]) == "--gain-blocks" && k + 1 < argc) {
 				if (sscanf(argv[++k], "%dx%d", &gbx, &gby) != 2 || gbx < 1 || gbx > 16 || gby < 1 || gby > 16) {
 					fprintf(stderr, "--gain-blocks wants BXxBY, each in [1, 16]; got %s\n", argv[k]); return 2;
@@ -152,7 +166,8 @@ int main(int argc, char** argv) {
 		}
 		argc = m;
 	}
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY]\n", argv[0]); return 2; }
+	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting]\n", argv[0]); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
@@ -169,8 +184,8 @@ int main(int argc, char** argv) {
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
-	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby);
-	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby);
+	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby, vig);
+	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig);
 
 	// ---- StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27)
 	std::vector<ImageRef> imgs;
@@ -236,12 +251,15 @@ int main(int argc, char** argv) {
 		bundle.calc_inverse_homo();
 		bundle.update_proj_range();
 		const bool blocks = gain && gbx * gby > 1;
-		const std::vector<float> gains = blocks ? hip_gain_compensate_blocks(bundle, gbx, gby) : gain ? hip_gain_compensate(bundle) : std::vector<float>();
-		Mat32f pano = blocks ? hip_blend(bundle, false, gains, gbx, gby) : hip_blend(bundle, false, gains);
+		std::array<float, 3> poly = {0.f, 0.f, 0.f};
+		const std::vector<float> gains = vig ? hip_vignette_compensate(bundle, poly) : blocks ? hip_gain_compensate_blocks(bundle, gbx, gby)
+		                               : gain ? hip_gain_compensate(bundle) : std::vector<float>();
+		Mat32f pano = vig ? hip_blend(bundle, false, gains, poly) : blocks ? hip_blend(bundle, false, gains, gbx, gby) : hip_blend(bundle, false, gains);
 		put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 		put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 		for (auto& t : to_mid) put(fo, t.data, 9);
 		put(fo, gains.data(), gains.size());
+		if (vig) put(fo, poly.data(), 3);
 		fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
 	} else {
 		put1<int32_t>(fo, 0); put1<int32_t>(fo, 0);
