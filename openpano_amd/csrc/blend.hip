@@ -217,6 +217,15 @@ __device__ __forceinline__ void apply_vignette(const float* __restrict__ g, cons
 #pragma unroll
 	for (int ch = 0; ch < 3; ++ch) { const float f = g[ch] / V; if (f != 1.f) col[ch] = fminf(col[ch] * f, 1.f); }
 }
+// The gain of mode GM (below) at a valid sample of image k -- ImageRef size w x h -- at image coordinates (r, c); gains: the
+// device table
+template <int GM>
+__device__ __forceinline__ void apply_gain_mode(const float* __restrict__ gains, int k, int n, int gbx, int gby, int w, int h, float r, float c,
+		float (&col)[3]) {
+	if (GM == GAIN_IMAGE) apply_gain(gains + 3 * (long long)k, col);
+	if (GM == GAIN_BLOCK) apply_block_gain(gains + 3 * (long long)k * gbx * gby, gbx, gby, w, h, r, c, col);
+	if (GM == GAIN_VIGNETTE) apply_vignette(gains + 3 * (long long)k, gains + 3 * (long long)n, w, h, r, c, col);
+}
 
 // ---- LinearBlender::run (blender.cc:24-96): thread per canvas pixel, images in index order.  GM: GAIN_IMAGE -- gains
 // (n x 3) scale every sample (op_blend_gains); GAIN_BLOCK -- gains (n x gby x gbx x 3) are interpolated at the sample
@@ -239,9 +248,7 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 			const BlendImg& im = imgs[k];
 			float r, c, col[3];
 			if (!linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col)) return;
-			if (GM == GAIN_IMAGE) apply_gain(gains + 3 * (long long)k, col);
-			if (GM == GAIN_BLOCK) apply_block_gain(gains + 3 * (long long)k * gbx * gby, gbx, gby, im.w, im.h, r, c, col);
-			if (GM == GAIN_VIGNETTE) apply_vignette(gains + 3 * (long long)k, gains + 3 * (long long)n, im.w, im.h, r, c, col);
+			apply_gain_mode<GM>(gains, k, n, gbx, gby, im.w, im.h, r, c, col);
 			float w = (float)(0.5 - fabs((double)(c / (float)im.w) - 0.5));
 			if (!ordered_input) w = (float)((double)w * (0.5 - fabs((double)(r / (float)im.h) - 0.5)));
 			s0 += col[0] * w; s1 += col[1] * w; s2 += col[2] * w;
@@ -261,17 +268,16 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 	}
 }
 
-// ---- exposure statistics (Brown & Lowe, IJCV 2007, section 6) for op_gain_overlap: thread per point of the canvas
+// ---- overlap statistics (op_gain_overlap, op_gain_block_overlap, op_vignette_overlap): thread per point of the canvas
 // lattice (i, j) = (ti, tj) * stride; at every point, the samples of the linear blender (linear_sample: same map, same
-// validity rules, same interpolation) of every covering image, and for every pair (a < b) of valid samples
-// N_ab += 1, S_ab[c] += col_a[c], S_ba[c] += col_b[c].  Colours are summed in fixed point, llrint(col * 2^32) as int64
-// (exact scaling; integer addition is associative, so the sums do not depend on the order the hardware adds them in):
-// a pair's sums are reduced across the wavefront (a row of 64 lattice points), then one 64-bit atomic per value.
-// The workgroup's cover set -- images whose ROI meets its 64 x 4 tile of lattice points -- is ONE bitmask over all n
-// images (dynamic LDS, ceil(n / 64) words), so pairs may straddle any 64-image word.  It is walked in chunks of
-// GAIN_CH images whose samples stay in registers (fully unrolled: constant indices, no scratch); the pairs of a chunk
-// with itself, then with every later covered image, one at a time.  A tile is usually covered by <= 4 images: one
-// chunk, every image sampled once.
+// validity rules, same interpolation) of every covering image, and for every pair (a < b) of valid samples the pair's
+// statistic.  Sums are fixed point, llrint(x * 2^32) as int64 (exact scaling; integer addition is associative, so the sums
+// do not depend on the order the hardware adds them in), reduced across the wavefront (a row of 64 lattice points), then
+// 64-bit atomics.  The workgroup's cover set -- images whose ROI meets its 64 x 4 tile of lattice points -- is ONE bitmask
+// over all n images (dynamic LDS, ceil(n / 64) words), so pairs may straddle any 64-image word.  It is walked in chunks of
+// GAIN_CH images whose samples stay in registers (fully unrolled: constant indices, no scratch); the pairs of a chunk with
+// itself, then with every later covered image, one at a time.  A tile is usually covered by <= 4 images: one chunk, every
+// image sampled once.
 constexpr int GAIN_CH = 8;
 constexpr double GAIN_FIX = 4294967296.0;       // 2^32
 constexpr int GAIN_MAX_IMAGES = 64 * 4096;       // cover bitmask: 4096 words = 32 KB of LDS
@@ -291,30 +297,17 @@ __device__ __forceinline__ long long wave_sum(long long v) {
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
 	return v;
 }
-// pair (a < b) at a * n - a (a + 1) / 2 + (b - a - 1) (include/openpano_hip.h); x / y: the samples of a / b, valid as
-// linear_sample said (va / vb)
-__device__ __forceinline__ void gain_pair(int a, int b, int n, bool va, const float (&x)[3], bool vb, const float (&y)[3],
-		unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
-	const bool both = va && vb;
-	const unsigned long long bal = __ballot(both);
-	if (!bal) return;                                   // wave-uniform
-	long long v[6];
-#pragma unroll
-	for (int ch = 0; ch < 3; ++ch) {
-		v[ch] = both ? llrint((double)x[ch] * GAIN_FIX) : 0;
-		v[3 + ch] = both ? llrint((double)y[ch] * GAIN_FIX) : 0;
-	}
-#pragma unroll
-	for (int q = 0; q < 6; ++q) v[q] = wave_sum(v[q]);
-	if ((threadIdx.x & 63) == 0) {
-		const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
-		atomicAdd(count + p, (unsigned long long)__popcll(bal));
-#pragma unroll
-		for (int q = 0; q < 6; ++q) atomicAdd(sums + 6 * p + q, (unsigned long long)v[q]);
-	}
-}
-__global__ void __launch_bounds__(256) k_gain_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
-		int H, int W, int stride, int lazy, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+// pair (a < b) of n images (include/openpano_hip.h)
+__host__ __device__ __forceinline__ long long pair_index(int a, int b, int n) { return (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1); }
+
+// The walk of the three statistics kernels over a statistic S.  A slot -- one image's sample at this lattice point -- has
+// two parts, of types S::P1 and S::P2, and the chunk keeps each part in its own plain array (an array of slot structs, or a
+// struct of the arrays, leaves the chunk in scratch memory).  S::clear(p1, p2): the slot without a sample.  S::sample(p1, p2,
+// im, lin): the slot of image im, where lin(im, r, c, col) is linear_sample at this lattice point; false: no valid sample,
+// or one the statistic refuses.  S::pair(a, b, n, va, p1a, p2a, vb, p1b, p2b): the statistic of the pair (a < b).
+template <typename S>
+__device__ __forceinline__ void overlap_walk(const BlendGeom& g, const BlendTrig& trig, const BlendImg* imgs, int n,
+		int H, int W, int stride, int lazy, const S& stat) {
 	extern __shared__ unsigned long long s_gcover[];
 	const int words = (n + 63) >> 6;
 	const int i = (blockIdx.y * 4 + (threadIdx.x >> 6)) * stride;
@@ -335,34 +328,70 @@ __global__ void __launch_bounds__(256) k_gain_overlap(BlendGeom g, BlendTrig tri
 	}
 	double hx, hy, hz;
 	proj2homo(g, trig, i, j, hx, hy, hz);
-	auto sample = [&](int k, float (&col)[3]) -> bool {
-		float r, c;
-		return live && linear_sample(imgs[k], i, j, hx, hy, hz, lazy, r, c, col);
-	};
+	auto lin = [&](const BlendImg& im, float& r, float& c, float (&col)[3]) { return live && linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col); };
 	int a0 = next_cover(s_gcover, words, 0);
 	while (a0 < n) {
-		int ka[GAIN_CH]; bool va[GAIN_CH]; float ca[GAIN_CH][3];
+		int ka[GAIN_CH]; bool va[GAIN_CH]; typename S::P1 p1a[GAIN_CH]; typename S::P2 p2a[GAIN_CH];
 		int k = a0;
 #pragma unroll
 		for (int s = 0; s < GAIN_CH; ++s) {
 			ka[s] = k;
-			va[s] = false;
-			if (k < n) { va[s] = sample(k, ca[s]); k = next_cover(s_gcover, words, k + 1); }
+			va[s] = false; stat.clear(p1a[s], p2a[s]);
+			if (k < n) { va[s] = stat.sample(p1a[s], p2a[s], imgs[k], lin); k = next_cover(s_gcover, words, k + 1); }
 		}
 #pragma unroll
 		for (int s = 0; s < GAIN_CH; ++s)
 #pragma unroll
 			for (int t = s + 1; t < GAIN_CH; ++t)
-				if (ka[t] < n) gain_pair(ka[s], ka[t], n, va[s], ca[s], va[t], ca[t], count, sums);
+				if (ka[t] < n) stat.pair(ka[s], ka[t], n, va[s], p1a[s], p2a[s], va[t], p1a[t], p2a[t]);
 		const int a1 = k;                               // first covered image after this chunk
 		for (int b = a1; b < n; b = next_cover(s_gcover, words, b + 1)) {
-			float cb[3];
-			const bool vb = sample(b, cb);
+			typename S::P1 p1b; typename S::P2 p2b;
+			stat.clear(p1b, p2b);
+			const bool vb = stat.sample(p1b, p2b, imgs[b], lin);
 #pragma unroll
-			for (int s = 0; s < GAIN_CH; ++s) gain_pair(ka[s], b, n, va[s], ca[s], vb, cb, count, sums);
+			for (int s = 0; s < GAIN_CH; ++s) stat.pair(ka[s], b, n, va[s], p1a[s], p2a[s], vb, p1b, p2b);
 		}
 		a0 = a1;
 	}
+}
+
+// ---- exposure statistics (Brown & Lowe, IJCV 2007, section 6) for op_gain_overlap: a slot holds its sample's colour; for
+// every pair (a < b) of valid samples N_ab += 1, S_ab[c] += col_a[c], S_ba[c] += col_b[c]: a pair's six sums are reduced
+// across the wavefront, then one 64-bit atomic per value.  x / y: the samples of a / b, valid as linear_sample said (va / vb)
+__device__ __forceinline__ void gain_pair(int a, int b, int n, bool va, const float (&x)[3], bool vb, const float (&y)[3],
+		unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+	const bool both = va && vb;
+	const unsigned long long bal = __ballot(both);
+	if (!bal) return;                                   // wave-uniform
+	long long v[6];
+#pragma unroll
+	for (int ch = 0; ch < 3; ++ch) {
+		v[ch] = both ? llrint((double)x[ch] * GAIN_FIX) : 0;
+		v[3 + ch] = both ? llrint((double)y[ch] * GAIN_FIX) : 0;
+	}
+#pragma unroll
+	for (int q = 0; q < 6; ++q) v[q] = wave_sum(v[q]);
+	if ((threadIdx.x & 63) == 0) {
+		const long long p = pair_index(a, b, n);
+		atomicAdd(count + p, (unsigned long long)__popcll(bal));
+#pragma unroll
+		for (int q = 0; q < 6; ++q) atomicAdd(sums + 6 * p + q, (unsigned long long)v[q]);
+	}
+}
+struct NoPart {};
+struct GainStat {                                       // a slot: the colour
+	using P1 = float[3]; using P2 = NoPart;
+	unsigned long long* count; unsigned long long* sums;
+	__device__ __forceinline__ void clear(P1&, P2&) const {}
+	template <typename L> __device__ __forceinline__ bool sample(P1& x, P2&, const BlendImg& im, L&& lin) const { float r, c; return lin(im, r, c, x); }
+	__device__ __forceinline__ void pair(int a, int b, int n, bool va, const P1& x, const P2&, bool vb, const P1& y, const P2&) const {
+		gain_pair(a, b, n, va, x, vb, y, count, sums);
+	}
+};
+__global__ void __launch_bounds__(256) k_gain_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
+		int H, int W, int stride, int lazy, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+	overlap_walk(g, trig, imgs, n, H, W, stride, lazy, GainStat{count, sums});
 }
 
 // ---- block statistics for op_gain_block_overlap: k_gain_overlap with every slot also carrying its sample's block
@@ -384,7 +413,7 @@ __device__ __forceinline__ void gain_block_pair(int a, int b, int n, int nblk, b
 		v[3 + ch] = both ? llrint((double)y[ch] * GAIN_FIX) : 0;
 	}
 	const int key = qa * nblk + qb;
-	const long long base = ((long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1)) * nblk * nblk;
+	const long long base = pair_index(a, b, n) * nblk * nblk;
 	while (bal) {                                       // wave-uniform: one round per distinct block pair
 		const int k0 = __builtin_amdgcn_readlane(key, __builtin_ctzll(bal));
 		const bool mine = both && key == k0;
@@ -401,67 +430,28 @@ __device__ __forceinline__ void gain_block_pair(int a, int b, int n, int nblk, b
 		bal &= ~mb;
 	}
 }
-__global__ void __launch_bounds__(256) k_gain_block_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
-		int H, int W, int stride, int lazy, int bx, int by, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
-	extern __shared__ unsigned long long s_gcover[];
-	const int words = (n + 63) >> 6;
-	const int nblk = bx * by;
-	const int i = (blockIdx.y * 4 + (threadIdx.x >> 6)) * stride;
-	const int j = (blockIdx.x * 64 + (threadIdx.x & 63)) * stride;
-	const bool live = i < H && j < W;
-	{	// tile_cover over all n images at once (as k_gain_overlap)
-		const int i0 = blockIdx.y * 4 * stride, j0 = blockIdx.x * 64 * stride, excl = lazy ? 1 : 0;
-		for (int k = (int)threadIdx.x; k < words * 64; k += 256) {
-			bool hit = false;
-			if (k < n) {
-				const BlendImg& im = imgs[k];
-				hit = im.x0 <= j0 + 63 * stride && im.x1 - excl >= j0 && im.y0 <= i0 + 3 * stride && im.y1 - excl >= i0;
-			}
-			const unsigned long long b = __ballot(hit);
-			if ((threadIdx.x & 63) == 0) s_gcover[k >> 6] = b;
-		}
-		__syncthreads();
-	}
-	double hx, hy, hz;
-	proj2homo(g, trig, i, j, hx, hy, hz);
-	auto sample = [&](int k, float (&col)[3], int& q) -> bool {
+struct GainBlockStat {                                  // a slot: the colour and its block
+	using P1 = float[3]; using P2 = int;
+	int bx, by; unsigned long long* count; unsigned long long* sums;
+	__device__ __forceinline__ void clear(P1&, P2& q) const { q = 0; }
+	template <typename L> __device__ __forceinline__ bool sample(P1& x, P2& q, const BlendImg& im, L&& lin) const {
 		float r, c;
-		q = 0;
-		const BlendImg& im = imgs[k];
-		if (!(live && linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col))) return false;
+		if (!lin(im, r, c, x)) return false;
 		q = gain_block_of(r, c, im.w, im.h, bx, by);
 		return true;
-	};
-	int a0 = next_cover(s_gcover, words, 0);
-	while (a0 < n) {
-		int ka[GAIN_CH], qa[GAIN_CH]; bool va[GAIN_CH]; float ca[GAIN_CH][3];
-		int k = a0;
-#pragma unroll
-		for (int s = 0; s < GAIN_CH; ++s) {
-			ka[s] = k;
-			va[s] = false; qa[s] = 0;
-			if (k < n) { va[s] = sample(k, ca[s], qa[s]); k = next_cover(s_gcover, words, k + 1); }
-		}
-#pragma unroll
-		for (int s = 0; s < GAIN_CH; ++s)
-#pragma unroll
-			for (int t = s + 1; t < GAIN_CH; ++t)
-				if (ka[t] < n) gain_block_pair(ka[s], ka[t], n, nblk, va[s], qa[s], ca[s], va[t], qa[t], ca[t], count, sums);
-		const int a1 = k;
-		for (int b = a1; b < n; b = next_cover(s_gcover, words, b + 1)) {
-			float cb[3]; int qb;
-			const bool vb = sample(b, cb, qb);
-#pragma unroll
-			for (int s = 0; s < GAIN_CH; ++s) gain_block_pair(ka[s], b, n, nblk, va[s], qa[s], ca[s], vb, qb, cb, count, sums);
-		}
-		a0 = a1;
 	}
+	__device__ __forceinline__ void pair(int a, int b, int n, bool va, const P1& x, P2 qa, bool vb, const P1& y, P2 qb) const {
+		gain_block_pair(a, b, n, bx * by, va, qa, x, vb, qb, y, count, sums);
+	}
+};
+__global__ void __launch_bounds__(256) k_gain_block_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
+		int H, int W, int stride, int lazy, int bx, int by, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
+	overlap_walk(g, trig, imgs, n, H, W, stride, lazy, GainBlockStat{bx, by, count, sums});
 }
 
-// ---- vignetting statistics for op_vignette_overlap: k_gain_overlap's lattice, cover walk and sampling, every slot carrying
-// the grey level Y and the radius rho of its sample instead of its colour; a sample whose largest channel exceeds `clip`
-// does not take part (saturated).  For every pair (a < b) of valid samples, with pa[k] = rho_a^k, pb[k] = rho_b^k
-// (fp64, pa[0] = 1, pa[k] = pa[k-1] * rho_a):
+// ---- vignetting statistics for op_vignette_overlap: every slot carries the grey level Y and the radius rho of its sample
+// instead of its colour; a sample whose largest channel exceeds `clip` does not take part (saturated).  For every pair
+// (a < b) of valid samples, with pa[k] = rho_a^k, pb[k] = rho_b^k (fp64, pa[0] = 1, pa[k] = pa[k-1] * rho_a):
 //   N += 1,  A_k += (Ya Ya) pb[k],  B_k += (Yb Yb) pa[k]  (k = 0..6),  C_ij += ((Ya Yb) pa[i]) pb[j]  (i, j = 0..3),
 // each product in fp64 in that order from the fp32 Y / rho, summed as llrint(x 2^32) in int64.  Every term lies in [0, 1]
 // (clip <= 1, rho clamped to [0, 1]) and the host caps the lattice at 2^30 points, so no sum can overflow.  Moment m of pair
@@ -493,66 +483,28 @@ __device__ __forceinline__ void vignette_pair(int a, int b, int n, bool va, floa
 		if (lane == m) mine = s;
 	}
 	if (lane <= VIG_MOMENTS) {
-		const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+		const long long p = pair_index(a, b, n);
 		atomicAdd(lane < VIG_MOMENTS ? moments + (long long)VIG_MOMENTS * p + lane : count + p, (unsigned long long)mine);
 	}
 }
-__global__ void __launch_bounds__(256) k_vignette_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
-		int H, int W, int stride, int lazy, float clip, unsigned long long* __restrict__ count, unsigned long long* __restrict__ moments) {
-	extern __shared__ unsigned long long s_gcover[];
-	const int words = (n + 63) >> 6;
-	const int i = (blockIdx.y * 4 + (threadIdx.x >> 6)) * stride;
-	const int j = (blockIdx.x * 64 + (threadIdx.x & 63)) * stride;
-	const bool live = i < H && j < W;
-	{	// tile_cover over all n images at once (as k_gain_overlap)
-		const int i0 = blockIdx.y * 4 * stride, j0 = blockIdx.x * 64 * stride, excl = lazy ? 1 : 0;
-		for (int k = (int)threadIdx.x; k < words * 64; k += 256) {
-			bool hit = false;
-			if (k < n) {
-				const BlendImg& im = imgs[k];
-				hit = im.x0 <= j0 + 63 * stride && im.x1 - excl >= j0 && im.y0 <= i0 + 3 * stride && im.y1 - excl >= i0;
-			}
-			const unsigned long long b = __ballot(hit);
-			if ((threadIdx.x & 63) == 0) s_gcover[k >> 6] = b;
-		}
-		__syncthreads();
-	}
-	double hx, hy, hz;
-	proj2homo(g, trig, i, j, hx, hy, hz);
-	auto sample = [&](int k, float& y, float& rho) -> bool {
+struct VignetteStat {                                   // a slot: the grey level and the radius
+	using P1 = float; using P2 = float;
+	float clip; unsigned long long* count; unsigned long long* moments;
+	__device__ __forceinline__ void clear(P1& y, P2& rho) const { y = 0.f; rho = 0.f; }
+	template <typename L> __device__ __forceinline__ bool sample(P1& y, P2& rho, const BlendImg& im, L&& lin) const {
 		float r, c, col[3];
-		y = 0.f; rho = 0.f;
-		const BlendImg& im = imgs[k];
-		if (!(live && linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col))) return false;
-		if (fmaxf(col[0], fmaxf(col[1], col[2])) > clip) return false;
+		if (!lin(im, r, c, col) || fmaxf(col[0], fmaxf(col[1], col[2])) > clip) return false;   // clip: saturated
 		y = vignette_grey(col);
 		rho = vignette_rho(r, c, im.w, im.h);
 		return true;
-	};
-	int a0 = next_cover(s_gcover, words, 0);
-	while (a0 < n) {
-		int ka[GAIN_CH]; bool va[GAIN_CH]; float ya[GAIN_CH], ra[GAIN_CH];
-		int k = a0;
-#pragma unroll
-		for (int s = 0; s < GAIN_CH; ++s) {
-			ka[s] = k;
-			va[s] = false; ya[s] = 0.f; ra[s] = 0.f;
-			if (k < n) { va[s] = sample(k, ya[s], ra[s]); k = next_cover(s_gcover, words, k + 1); }
-		}
-#pragma unroll
-		for (int s = 0; s < GAIN_CH; ++s)
-#pragma unroll
-			for (int t = s + 1; t < GAIN_CH; ++t)
-				if (ka[t] < n) vignette_pair(ka[s], ka[t], n, va[s], ya[s], ra[s], va[t], ya[t], ra[t], count, moments);
-		const int a1 = k;                               // first covered image after this chunk
-		for (int b = a1; b < n; b = next_cover(s_gcover, words, b + 1)) {
-			float yb, rb;
-			const bool vb = sample(b, yb, rb);
-#pragma unroll
-			for (int s = 0; s < GAIN_CH; ++s) vignette_pair(ka[s], b, n, va[s], ya[s], ra[s], vb, yb, rb, count, moments);
-		}
-		a0 = a1;
 	}
+	__device__ __forceinline__ void pair(int a, int b, int n, bool va, P1 ya, P2 ra, bool vb, P1 yb, P2 rb) const {
+		vignette_pair(a, b, n, va, ya, ra, vb, yb, rb, count, moments);
+	}
+};
+__global__ void __launch_bounds__(256) k_vignette_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
+		int H, int W, int stride, int lazy, float clip, unsigned long long* __restrict__ count, unsigned long long* __restrict__ moments) {
+	overlap_walk(g, trig, imgs, n, H, W, stride, lazy, VignetteStat{clip, count, moments});
 }
 
 // ---- create_first_level + update_weight_map (multiband.cc:19-56,125-143) in ONE pass, thread per canvas pixel:
@@ -593,9 +545,7 @@ __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig t
 			float col[3];
 			bool ok = interpolate(im.data, im.mh, im.mw, (float)oy, (float)ox, col);
 			if (ok) { float mn = fminf(col[0], fminf(col[1], col[2])); if (mn < 0) ok = false; }
-			if (GM == GAIN_IMAGE && ok) apply_gain(gains + 3 * (long long)k, col);
-			if (GM == GAIN_BLOCK && ok) apply_block_gain(gains + 3 * (long long)k * gbx * gby, gbx, gby, im.w, im.h, (float)oy, (float)ox, col);
-			if (GM == GAIN_VIGNETTE && ok) apply_vignette(gains + 3 * (long long)k, gains + 3 * (long long)n, im.w, im.h, (float)oy, (float)ox, col);
+			if (ok) apply_gain_mode<GM>(gains, k, n, gbx, gby, im.w, im.h, (float)oy, (float)ox, col);
 			float4 px = make_float4(0.f, 0.f, 0.f, 0.f);
 			if (ok) {
 				const double x = ox / (double)im.w - 0.5, y = oy / (double)im.h - 0.5;
@@ -1245,10 +1195,10 @@ int check_blend_args(const char* who, const op_blend_geom* g) {
 	return OP_OK;
 }
 
-// op_blend (gains == NULL), op_blend_gains (gbx == 0, gains: n x 3 on the host), op_blend_block_gains (gbx, gby >= 1,
-// gains: n x gby x gbx x 3 on the host) and op_blend_vignette (vignette: n x 3 gains then a1..a3, 3 n + 3 host floats)
-int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
-		int gbx, int gby, const char* who, op_canvas** out, const float* vignette = nullptr) {
+// The blend of gain mode gm with the host table `gains`: GAIN_NONE (op_blend; no table), GAIN_IMAGE (op_blend_gains; n x 3),
+// GAIN_BLOCK (op_blend_block_gains; n x gby x gbx x 3) or GAIN_VIGNETTE (op_blend_vignette; n x 3 gains then a1..a3)
+int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int gm, const float* gains,
+		int gbx, int gby, const char* who, op_canvas** out) {
 	int rc = check_blend_args(who, g);
 	if (rc != OP_OK) return rc;
 	HIPCHK(hipSetDevice(ctx->device));
@@ -1264,9 +1214,7 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	rc = upload_images(ctx, who, g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
 	if (rc != OP_OK) return rc;
 	float* d_gains = nullptr;
-	const int gm = vignette ? GAIN_VIGNETTE : (!gains ? GAIN_NONE : (gbx > 0 ? GAIN_BLOCK : GAIN_IMAGE));
-	if (vignette) gains = vignette;
-	if (gains) {                 // the whole table, once per call
+	if (gm != GAIN_NONE) {       // the whole table, once per call
 		const size_t ng = gm == GAIN_VIGNETTE ? 3 * (size_t)n + 3 : 3 * (size_t)n * (gm == GAIN_BLOCK ? (size_t)gbx * gby : 1);
 		HIPCHK(pool_alloc((void**)&d_gains, sizeof(float) * ng)); fr.v.push_back(d_gains);
 		HIPCHK(hipMemcpyAsync(d_gains, gains, sizeof(float) * ng, hipMemcpyHostToDevice, st));
@@ -1284,12 +1232,14 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	}
 #define BCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
 	pool_free(cv->data); delete cv; return OP_ERR_HIP; } } while (0)
+	// the instances of the gain mode (gbx / gby are read by GAIN_BLOCK only)
+	auto linear = k_blend_linear<GAIN_NONE>; auto first = k_mb_first_fused<GAIN_NONE>;
+	if (gm == GAIN_IMAGE) { linear = k_blend_linear<GAIN_IMAGE>; first = k_mb_first_fused<GAIN_IMAGE>; }
+	else if (gm == GAIN_BLOCK) { linear = k_blend_linear<GAIN_BLOCK>; first = k_mb_first_fused<GAIN_BLOCK>; }
+	else if (gm == GAIN_VIGNETTE) { linear = k_blend_linear<GAIN_VIGNETTE>; first = k_mb_first_fused<GAIN_VIGNETTE>; }
 	if (cfg->MULTIBAND <= 0) {
 		ProfScope ps(ctx, "blend linear");
-		if (gm == GAIN_VIGNETTE) hipLaunchKernelGGL(k_blend_linear<GAIN_VIGNETTE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, 0, 0);
-		else if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_blend_linear<GAIN_BLOCK>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
-		else if (gm == GAIN_IMAGE) hipLaunchKernelGGL(k_blend_linear<GAIN_IMAGE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, 0, 0);
-		else hipLaunchKernelGGL(k_blend_linear<GAIN_NONE>, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, nullptr, 0, 0);
+		hipLaunchKernelGGL(linear, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
 		BCHK(hipGetLastError());
 	} else {
 		const int L = cfg->MULTIBAND;
@@ -1306,10 +1256,7 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 		const dim3 rgrid((unsigned)((max_roi + 255) / 256), n);
 		{ ProfScope ps(ctx, "multiband first level");
 		  const dim3 fgrid((W + 1 + 63) / 64, (H + 1 + 3) / 4);
-		  if (gm == GAIN_VIGNETTE) hipLaunchKernelGGL(k_mb_first_fused<GAIN_VIGNETTE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, 0, 0);
-		  else if (gm == GAIN_BLOCK) hipLaunchKernelGGL(k_mb_first_fused<GAIN_BLOCK>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, gbx, gby);
-		  else if (gm == GAIN_IMAGE) hipLaunchKernelGGL(k_mb_first_fused<GAIN_IMAGE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, 0, 0);
-		  else hipLaunchKernelGGL(k_mb_first_fused<GAIN_NONE>, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, nullptr, 0, 0);
+		  hipLaunchKernelGGL(first, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, gbx, gby);
 		  BCHK(hipGetLastError()); }
 		bool band0_done = false;                 // level 0's band written by the fused blur
 		for (int level = 0; level < L; ++level) {
@@ -1391,33 +1338,83 @@ int check_lens_frame(const char* who, const op_blend_image* imgs, int n) {
 	return OP_OK;
 }
 
+// every gain of a host table (count floats, per_image of them per image; NULL: none) finite and positive
+int check_gains(const char* who, const float* gains, long long count, long long per_image) {
+	for (long long e = 0; gains && e < count; ++e)
+		if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
+			OP_FAIL(OP_ERR_INVALID, std::string(who) + ": gain " + std::to_string(e) + " (image " + std::to_string(e / per_image) + ") is not finite and positive");
+	return OP_OK;
+}
+
+// The host side of op_gain_overlap, op_gain_block_overlap and op_vignette_overlap after their own checks: `entries` counts
+// and entries x per values, zeroed on the device, filled by kernel(bg, trig, images, n, H, W, stride, LAZY_READ, extra...,
+// counts, values) over the canvas lattice of `stride`, copied to count / values.  cap_lattice: more than VIG_MAX_LATTICE
+// lattice points are refused (the bound of the vignetting sums).
+template <typename K, typename... X>
+int overlap_stats(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride, const char* who,
+		const char* label, long long entries, int per, bool cap_lattice, int64_t* count, int64_t* values, K kernel, X... extra) {
+	if (entries == 0) return OP_OK;                     // one image: no pair
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	int H, W;
+	int rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
+	if (rc != OP_OK) return rc;
+	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, std::string(who) + ": empty canvas");
+	// a stride beyond the canvas leaves the lattice {(0, 0)} -- clamped so that lattice coordinates stay far from overflow
+	stride = std::min(stride, std::max(H, W));
+	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
+	if (cap_lattice && (long long)hs_ * ws_ > VIG_MAX_LATTICE)
+		OP_FAIL(OP_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string((long long)hs_ * ws_) + " lattice points exceed 2^30 (raise the stride)");
+	Freer fr;
+	std::vector<BlendImg> h_imgs;
+	long long roi_total = 0, max_roi = 0;
+	BlendImg* d_imgs = nullptr;
+	rc = upload_images(ctx, who, g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
+	if (rc != OP_OK) return rc;
+	unsigned long long* d_stats = nullptr;         // entries counts, then entries x per values
+	const size_t stat_bytes = sizeof(unsigned long long) * (1 + per) * (size_t)entries;
+	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
+	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
+	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
+	BlendTrig trig{nullptr, nullptr, 0, 0};
+	if (bg.method != 0) {            // the blend's own tables (same key: canvas + 1), so a following blend finds them cached
+		HostScope hs(ctx, "blend trig tables (host)");
+		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
+	}
+	{ ProfScope ps(ctx, label);
+	  hipLaunchKernelGGL(kernel, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * ((n + 63) / 64), st,
+	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, extra..., d_stats, d_stats + entries);
+	  HIPCHK(hipGetLastError()); }
+	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)entries, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(values, d_stats + entries, sizeof(int64_t) * per * (size_t)entries, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	resolve_profile(ctx);
+	return OP_OK;
+}
+
 }	// namespace
 
 extern "C" {
 
 int op_blend(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, op_canvas** out) {
 	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend: bad argument");
-	return blend_impl(ctx, cfg, g, imgs, n, nullptr, 0, 0, "op_blend", out);
+	return blend_impl(ctx, cfg, g, imgs, n, GAIN_NONE, nullptr, 0, 0, "op_blend", out);
 }
 
 int op_blend_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains, op_canvas** out) {
 	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend_gains: bad argument");
-	if (gains)
-		for (int e = 0; e < 3 * n; ++e)
-			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
-				OP_FAIL(OP_ERR_INVALID, "op_blend_gains: gain " + std::to_string(e) + " (image " + std::to_string(e / 3) + ") is not finite and positive");
-	return blend_impl(ctx, cfg, g, imgs, n, gains, 0, 0, "op_blend_gains", out);
+	const int rc = check_gains("op_blend_gains", gains, 3ll * n, 3);
+	if (rc != OP_OK) return rc;
+	return blend_impl(ctx, cfg, g, imgs, n, gains ? GAIN_IMAGE : GAIN_NONE, gains, 0, 0, "op_blend_gains", out);
 }
 
 int op_blend_block_gains(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int bx, int by,
 		const float* gains, op_canvas** out) {
 	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS)
 		OP_FAIL(OP_ERR_INVALID, "op_blend_block_gains: bad argument");
-	if (gains)
-		for (long long e = 0; e < 3ll * n * bx * by; ++e)
-			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
-				OP_FAIL(OP_ERR_INVALID, "op_blend_block_gains: gain " + std::to_string(e) + " (image " + std::to_string(e / (3 * bx * by)) + ") is not finite and positive");
-	return blend_impl(ctx, cfg, g, imgs, n, gains, bx, by, "op_blend_block_gains", out);
+	const int rc = check_gains("op_blend_block_gains", gains, 3ll * n * bx * by, 3ll * bx * by);
+	if (rc != OP_OK) return rc;
+	return blend_impl(ctx, cfg, g, imgs, n, gains ? GAIN_BLOCK : GAIN_NONE, gains, bx, by, "op_blend_block_gains", out);
 }
 
 int op_blend_vignette(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
@@ -1425,17 +1422,14 @@ int op_blend_vignette(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g,
 	if (!ctx || !cfg || !g || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_blend_vignette: bad argument");
 	int rc = check_lens_frame("op_blend_vignette", imgs, n);
 	if (rc != OP_OK) return rc;
+	rc = check_gains("op_blend_vignette", gains, 3ll * n, 3);
+	if (rc != OP_OK) return rc;
 	std::vector<float> table(3 * (size_t)n + 3, 1.f);   // gains (NULL = 1), then a1..a3 (NULL = 0)
-	if (gains)
-		for (int e = 0; e < 3 * n; ++e) {
-			if (!std::isfinite(gains[e]) || !(gains[e] > 0.f))
-				OP_FAIL(OP_ERR_INVALID, "op_blend_vignette: gain " + std::to_string(e) + " (image " + std::to_string(e / 3) + ") is not finite and positive");
-			table[e] = gains[e];
-		}
+	if (gains) std::copy(gains, gains + 3 * (size_t)n, table.begin());
 	for (int j = 0; j < 3; ++j) table[3 * (size_t)n + j] = poly ? poly[j] : 0.f;
 	const double a[3] = {table[3 * (size_t)n], table[3 * (size_t)n + 1], table[3 * (size_t)n + 2]};
 	if (!vignette_curve_positive(a)) OP_FAIL(OP_ERR_INVALID, "op_blend_vignette: the curve is not finite and positive on [0, 1]");
-	return blend_impl(ctx, cfg, g, imgs, n, nullptr, 0, 0, "op_blend_vignette", out, table.data());
+	return blend_impl(ctx, cfg, g, imgs, n, GAIN_VIGNETTE, table.data(), 0, 0, "op_blend_vignette", out);
 }
 
 int op_vignette_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
@@ -1446,91 +1440,20 @@ int op_vignette_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* 
 	if (rc != OP_OK) return rc;
 	rc = check_lens_frame("op_vignette_overlap", imgs, n);
 	if (rc != OP_OK) return rc;
-	const int words = (n + 63) / 64;
-	if (words > GAIN_MAX_IMAGES / 64) OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
-	const long long npairs = (long long)n * (n - 1) / 2;
-	if (npairs == 0) return OP_OK;
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t st = ctx->stream;
-	int H, W;
-	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
-	if (rc != OP_OK) return rc;
-	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, "op_vignette_overlap: empty canvas");
-	stride = std::min(stride, std::max(H, W));
-	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
-	if ((long long)hs_ * ws_ > VIG_MAX_LATTICE)
-		OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_overlap: " + std::to_string((long long)hs_ * ws_) + " lattice points exceed 2^30 (raise the stride)");
-	Freer fr;
-	std::vector<BlendImg> h_imgs;
-	long long roi_total = 0, max_roi = 0;
-	BlendImg* d_imgs = nullptr;
-	rc = upload_images(ctx, "op_vignette_overlap", g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
-	if (rc != OP_OK) return rc;
-	unsigned long long* d_stats = nullptr;         // npairs counts, then npairs x 30 moments
-	const size_t stat_bytes = sizeof(unsigned long long) * (1 + VIG_MOMENTS) * (size_t)npairs;
-	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
-	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
-	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
-	BlendTrig trig{nullptr, nullptr, 0, 0};
-	if (bg.method != 0) {
-		HostScope hs(ctx, "blend trig tables (host)");
-		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
-	}
-	{ ProfScope ps(ctx, "vignette overlap");
-	  hipLaunchKernelGGL(k_vignette_overlap, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * words, st,
-	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, clip, d_stats, d_stats + npairs);
-	  HIPCHK(hipGetLastError()); }
-	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)npairs, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(moments, d_stats + npairs, sizeof(int64_t) * VIG_MOMENTS * (size_t)npairs, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	resolve_profile(ctx);
-	return OP_OK;
+	if (n > GAIN_MAX_IMAGES) OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
+	return overlap_stats(ctx, cfg, g, imgs, n, stride, "op_vignette_overlap", "vignette overlap", (long long)n * (n - 1) / 2, VIG_MOMENTS, true,
+	                     count, moments, k_vignette_overlap, clip);
 }
 
 int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
 		int64_t* count, int64_t* sums) {
 	if (!ctx || !cfg || !g || !imgs || n < 1 || stride < 1 || (n > 1 && (!count || !sums)))
 		OP_FAIL(OP_ERR_INVALID, "op_gain_overlap: bad argument");
-	int rc = check_blend_args("op_gain_overlap", g);
+	const int rc = check_blend_args("op_gain_overlap", g);
 	if (rc != OP_OK) return rc;
-	const int words = (n + 63) / 64;
-	if (words > GAIN_MAX_IMAGES / 64) OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
-	const long long npairs = (long long)n * (n - 1) / 2;
-	if (npairs == 0) return OP_OK;
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t st = ctx->stream;
-	int H, W;
-	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
-	if (rc != OP_OK) return rc;
-	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, "op_gain_overlap: empty canvas");
-	Freer fr;
-	std::vector<BlendImg> h_imgs;
-	long long roi_total = 0, max_roi = 0;
-	BlendImg* d_imgs = nullptr;
-	rc = upload_images(ctx, "op_gain_overlap", g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
-	if (rc != OP_OK) return rc;
-	unsigned long long* d_stats = nullptr;         // npairs counts, then npairs x 6 sums
-	const size_t stat_bytes = sizeof(unsigned long long) * 7 * (size_t)npairs;
-	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
-	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
-	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
-	BlendTrig trig{nullptr, nullptr, 0, 0};
-	if (bg.method != 0) {            // the blend's own tables (same key: canvas + 1), so a following blend finds them cached
-		HostScope hs(ctx, "blend trig tables (host)");
-		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
-	}
-	// a stride beyond the canvas leaves the lattice {(0, 0)} -- clamped so that lattice coordinates stay far from overflow
-	stride = std::min(stride, std::max(H, W));
-	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
-	{ ProfScope ps(ctx, "gain overlap");
-	  hipLaunchKernelGGL(k_gain_overlap, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * words, st,
-	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, d_stats, d_stats + npairs);
-	  HIPCHK(hipGetLastError()); }
-	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)npairs, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(sums, d_stats + npairs, sizeof(int64_t) * 6 * (size_t)npairs, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	resolve_profile(ctx);
-	return OP_OK;
+	if (n > GAIN_MAX_IMAGES) OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
+	return overlap_stats(ctx, cfg, g, imgs, n, stride, "op_gain_overlap", "gain overlap", (long long)n * (n - 1) / 2, 6, false,
+	                     count, sums, k_gain_overlap);
 }
 
 }	// extern "C"
@@ -1563,144 +1486,35 @@ bool gain_cholesky_solve(std::vector<double>& A, std::vector<double>& rhs, int m
 	}
 	return true;
 }
-}	// namespace
 
-extern "C" {
-
-// Gain compensation (Brown & Lowe, IJCV 2007, section 6), host only: minimise
-//   e = 1/2 sum_a sum_{b != a} N_ab [ (g_a I_ab - g_b I_ba)^2 / sigma_n^2 + (1 - g_a)^2 / sigma_g^2 ]
-// through its normal equations (for every a, over b != a)
-//   sum_b N_ab [ (2 I_ab^2 / sigma_n^2 + 1 / sigma_g^2) g_a - (2 I_ab I_ba / sigma_n^2) g_b ] = sum_b N_ab / sigma_g^2,
-// I_ab = S_ab / (2^32 N_ab) the mean of image a over its overlap with b.  The matrix is symmetric and, for sigma_g > 0,
-// positive definite on the images with any overlap; those without are g = 1 and left out.  Cholesky, fp64, fixed loop
-// order: the gains are a function of the statistics alone.
-int op_gain_solve(int n, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, int per_channel, float* gains) {
-	if (n < 1 || !gains || (n > 1 && (!count || !sums)) || !(sigma_n > 0) || !(sigma_g > 0) || !std::isfinite(sigma_n) || !std::isfinite(sigma_g) ||
-			(per_channel != 0 && per_channel != 1))
-		OP_FAIL(OP_ERR_INVALID, "op_gain_solve: bad argument");
-	const long long npairs = (long long)n * (n - 1) / 2;
-	for (long long p = 0; p < npairs; ++p)
-		if (count[p] < 0) OP_FAIL(OP_ERR_INVALID, "op_gain_solve: negative overlap count at pair " + std::to_string(p));
-	// the active images (any overlap), in index order
-	std::vector<int> slot(n, -1), act;
+// The active images of a solve -- those in a pair (a < b) for which overlaps(a, b, p) holds, p = pair_index(a, b, n), asked
+// once per pair in pair order -- in index order; slot[k] is image k's place among them, -1 for the others.
+template <typename F>
+std::vector<int> active_images(int n, std::vector<int>& slot, F&& overlaps) {
+	slot.assign(n, -1);
 	for (int a = 0; a < n; ++a)
 		for (int b = a + 1; b < n; ++b)
-			if (count[(long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1)] > 0) { slot[a] = slot[b] = 0; }
+			if (overlaps(a, b, pair_index(a, b, n))) slot[a] = slot[b] = 0;
+	std::vector<int> act;
 	for (int a = 0; a < n; ++a) if (slot[a] == 0) { slot[a] = (int)act.size(); act.push_back(a); }
-	const int m = (int)act.size();
-	for (int e = 0; e < 3 * n; ++e) gains[e] = 1.f;
-	if (m == 0) return OP_OK;
-	const double inv_n2 = 1.0 / (sigma_n * sigma_n), inv_g2 = 1.0 / (sigma_g * sigma_g);
-	std::vector<double> A((size_t)m * m), rhs(m);
-	const int nsolve = per_channel ? 3 : 1;
-	for (int ch = 0; ch < nsolve; ++ch) {
-		std::fill(A.begin(), A.end(), 0.0); std::fill(rhs.begin(), rhs.end(), 0.0);
-		for (int a = 0; a < n; ++a)
-			for (int b = a + 1; b < n; ++b) {
-				const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
-				if (count[p] <= 0) continue;
-				const double N = (double)count[p], den = GAIN_FIX * N;
-				const int64_t* S = sums + 6 * p;
-				double Iab, Iba;
-				if (per_channel) { Iab = (double)S[ch] / den; Iba = (double)S[3 + ch] / den; }
-				else { Iab = ((double)(S[0] + S[1] + S[2]) / 3.0) / den; Iba = ((double)(S[3] + S[4] + S[5]) / 3.0) / den; }
-				const int sa = slot[a], sb = slot[b];
-				A[(size_t)sa * m + sa] += N * (2.0 * Iab * Iab * inv_n2 + inv_g2);
-				A[(size_t)sb * m + sb] += N * (2.0 * Iba * Iba * inv_n2 + inv_g2);
-				const double off = N * (2.0 * Iab * Iba * inv_n2);
-				A[(size_t)sa * m + sb] -= off;
-				A[(size_t)sb * m + sa] -= off;
-				rhs[sa] += N * inv_g2;
-				rhs[sb] += N * inv_g2;
-			}
-		if (!gain_cholesky_solve(A, rhs, m)) OP_FAIL(OP_ERR_INVALID, "op_gain_solve: system not positive definite (inconsistent statistics)");
-		for (int i = 0; i < m; ++i) {
-			const float gv = (float)rhs[i];
-			if (per_channel) gains[3 * act[i] + ch] = gv;
-			else gains[3 * act[i]] = gains[3 * act[i] + 1] = gains[3 * act[i] + 2] = gv;
-		}
-	}
-	return OP_OK;
+	return act;
 }
 
-int op_gain_block_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
-		int bx, int by, int64_t* count, int64_t* sums) {
-	if (!ctx || !cfg || !g || !imgs || n < 1 || stride < 1 || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS ||
-			(n > 1 && (!count || !sums)))
-		OP_FAIL(OP_ERR_INVALID, "op_gain_block_overlap: bad argument");
-	int rc = check_blend_args("op_gain_block_overlap", g);
-	if (rc != OP_OK) return rc;
-	const int words = (n + 63) / 64;
-	if (words > GAIN_MAX_IMAGES / 64) OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
-	const long long npairs = (long long)n * (n - 1) / 2, nblk = (long long)bx * by, entries = npairs * nblk * nblk;
-	if (entries > GAIN_BLOCK_MAX_ENTRIES)
-		OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_overlap: " + std::to_string(entries) + " unit-pair entries (pairs x (bx by)^2) exceed " +
-		        std::to_string(GAIN_BLOCK_MAX_ENTRIES));
-	if (npairs == 0) return OP_OK;
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t st = ctx->stream;
-	int H, W;
-	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
-	if (rc != OP_OK) return rc;
-	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, "op_gain_block_overlap: empty canvas");
-	Freer fr;
-	std::vector<BlendImg> h_imgs;
-	long long roi_total = 0, max_roi = 0;
-	BlendImg* d_imgs = nullptr;
-	rc = upload_images(ctx, "op_gain_block_overlap", g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
-	if (rc != OP_OK) return rc;
-	unsigned long long* d_stats = nullptr;         // entries counts, then entries x 6 sums
-	const size_t stat_bytes = sizeof(unsigned long long) * 7 * (size_t)entries;
-	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
-	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
-	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
-	BlendTrig trig{nullptr, nullptr, 0, 0};
-	if (bg.method != 0) {
-		HostScope hs(ctx, "blend trig tables (host)");
-		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
-	}
-	stride = std::min(stride, std::max(H, W));
-	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
-	{ ProfScope ps(ctx, "gain block overlap");
-	  hipLaunchKernelGGL(k_gain_block_overlap, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * words, st,
-	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, bx, by, d_stats, d_stats + entries);
-	  HIPCHK(hipGetLastError()); }
-	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)entries, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(sums, d_stats + entries, sizeof(int64_t) * 6 * (size_t)entries, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	resolve_profile(ctx);
-	return OP_OK;
-}
-
-// Block gain compensation, host only: op_gain_solve's normal equations over units (k, q) -- entry e = p B^2 + qa B + qb
-// couples unit (a, qa) with (b, qb) exactly as pair p couples a with b there, in the same pair order -- plus, for every
-// 4-neighbour edge q ~ q' of an active image k, 2 lambda_k / sigma_s^2 on both diagonals and -2 lambda_k / sigma_s^2 off
-// them, lambda_k = M_k / B, M_k = the overlap samples of k over all its pairs.  With B = 1 there are no edges and the
-// matrix is op_gain_solve's, built in the same order and solved by the same code: the same floats.
-int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, double sigma_s,
-		int per_channel, float* gains) {
-	if (n < 1 || !gains || (n > 1 && (!count || !sums)) || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS ||
-			!(sigma_n > 0) || !(sigma_g > 0) || !(sigma_s > 0) || !std::isfinite(sigma_n) || !std::isfinite(sigma_g) || !std::isfinite(sigma_s) ||
-			(per_channel != 0 && per_channel != 1))
-		OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: bad argument");
+// The normal equations of op_gain_block_solve (below) and their solve, after the entry point's own checks: op_gain_solve is
+// the case bx = by = 1.  `who` prefixes the failure.
+int gain_unit_solve(const char* who, int n, int bx, int by, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g,
+		double sigma_s, int per_channel, float* gains) {
 	const int B = bx * by;
-	if ((long long)n * B > GAIN_BLOCK_MAX_UNKNOWNS)
-		OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_solve: " + std::to_string((long long)n * B) + " units (n bx by) exceed the dense solve's " +
-		        std::to_string(GAIN_BLOCK_MAX_UNKNOWNS));
-	const long long npairs = (long long)n * (n - 1) / 2, B2 = (long long)B * B, entries = npairs * B2;
-	for (long long e = 0; e < entries; ++e)
-		if (count[e] < 0) OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: negative overlap count at entry " + std::to_string(e));
-	// the active images (any overlap) in index order, and M_k
-	std::vector<int> slot(n, -1), act;
+	const long long B2 = (long long)B * B;
+	// the active images, and M_k
 	std::vector<double> M(n, 0.0);
-	for (int a = 0; a < n; ++a)
-		for (int b = a + 1; b < n; ++b) {
-			const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
-			int64_t N = 0;
-			for (long long e = p * B2; e < (p + 1) * B2; ++e) N += count[e];
-			if (N > 0) { slot[a] = slot[b] = 0; M[a] += (double)N; M[b] += (double)N; }
-		}
-	for (int a = 0; a < n; ++a) if (slot[a] == 0) { slot[a] = (int)act.size(); act.push_back(a); }
+	std::vector<int> slot;
+	const std::vector<int> act = active_images(n, slot, [&](int a, int b, long long p) {
+		int64_t N = 0;
+		for (long long e = p * B2; e < (p + 1) * B2; ++e) N += count[e];
+		if (N > 0) { M[a] += (double)N; M[b] += (double)N; }
+		return N > 0;
+	});
 	const int m = (int)act.size() * B;
 	for (long long e = 0; e < 3ll * n * B; ++e) gains[e] = 1.f;
 	if (m == 0) return OP_OK;
@@ -1711,7 +1525,7 @@ int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64
 		std::fill(A.begin(), A.end(), 0.0); std::fill(rhs.begin(), rhs.end(), 0.0);
 		for (int a = 0; a < n; ++a)
 			for (int b = a + 1; b < n; ++b) {
-				const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
+				const long long p = pair_index(a, b, n);
 				for (int qa = 0; qa < B; ++qa)
 					for (int qb = 0; qb < B; ++qb) {
 						const long long e = p * B2 + (long long)qa * B + qb;
@@ -1744,7 +1558,7 @@ int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64
 					}
 				}
 		}
-		if (!gain_cholesky_solve(A, rhs, m)) OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: system not positive definite (inconsistent statistics)");
+		if (!gain_cholesky_solve(A, rhs, m)) OP_FAIL(OP_ERR_INVALID, std::string(who) + ": system not positive definite (inconsistent statistics)");
 		for (int s = 0; s < (int)act.size(); ++s)
 			for (int q = 0; q < B; ++q) {
 				const float gv = (float)rhs[(size_t)s * B + q];
@@ -1754,6 +1568,62 @@ int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64
 			}
 	}
 	return OP_OK;
+}
+
+}	// namespace
+
+extern "C" {
+
+// Gain compensation (Brown & Lowe, IJCV 2007, section 6), host only: minimise
+//   e = 1/2 sum_a sum_{b != a} N_ab [ (g_a I_ab - g_b I_ba)^2 / sigma_n^2 + (1 - g_a)^2 / sigma_g^2 ]
+// through its normal equations (for every a, over b != a)
+//   sum_b N_ab [ (2 I_ab^2 / sigma_n^2 + 1 / sigma_g^2) g_a - (2 I_ab I_ba / sigma_n^2) g_b ] = sum_b N_ab / sigma_g^2,
+// I_ab = S_ab / (2^32 N_ab) the mean of image a over its overlap with b.  The matrix is symmetric and, for sigma_g > 0,
+// positive definite on the images with any overlap; those without are g = 1 and left out.  Cholesky, fp64, fixed loop
+// order: the gains are a function of the statistics alone.
+int op_gain_solve(int n, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, int per_channel, float* gains) {
+	if (n < 1 || !gains || (n > 1 && (!count || !sums)) || !(sigma_n > 0) || !(sigma_g > 0) || !std::isfinite(sigma_n) || !std::isfinite(sigma_g) ||
+			(per_channel != 0 && per_channel != 1))
+		OP_FAIL(OP_ERR_INVALID, "op_gain_solve: bad argument");
+	const long long npairs = (long long)n * (n - 1) / 2;
+	for (long long p = 0; p < npairs; ++p)
+		if (count[p] < 0) OP_FAIL(OP_ERR_INVALID, "op_gain_solve: negative overlap count at pair " + std::to_string(p));
+	return gain_unit_solve("op_gain_solve", n, 1, 1, count, sums, sigma_n, sigma_g, 1.0, per_channel, gains);   // one unit per image: no edges
+}
+
+int op_gain_block_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
+		int bx, int by, int64_t* count, int64_t* sums) {
+	if (!ctx || !cfg || !g || !imgs || n < 1 || stride < 1 || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS ||
+			(n > 1 && (!count || !sums)))
+		OP_FAIL(OP_ERR_INVALID, "op_gain_block_overlap: bad argument");
+	const int rc = check_blend_args("op_gain_block_overlap", g);
+	if (rc != OP_OK) return rc;
+	if (n > GAIN_MAX_IMAGES) OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
+	const long long npairs = (long long)n * (n - 1) / 2, nblk = (long long)bx * by, entries = npairs * nblk * nblk;
+	if (entries > GAIN_BLOCK_MAX_ENTRIES)
+		OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_overlap: " + std::to_string(entries) + " unit-pair entries (pairs x (bx by)^2) exceed " +
+		        std::to_string(GAIN_BLOCK_MAX_ENTRIES));
+	return overlap_stats(ctx, cfg, g, imgs, n, stride, "op_gain_block_overlap", "gain block overlap", entries, 6, false, count, sums,
+	                     k_gain_block_overlap, bx, by);
+}
+
+// Block gain compensation, host only: op_gain_solve's normal equations over units (k, q) -- entry e = p B^2 + qa B + qb
+// couples unit (a, qa) with (b, qb) exactly as pair p couples a with b there, in the same pair order -- plus, for every
+// 4-neighbour edge q ~ q' of an active image k, 2 lambda_k / sigma_s^2 on both diagonals and -2 lambda_k / sigma_s^2 off
+// them, lambda_k = M_k / B, M_k = the overlap samples of k over all its pairs.  With B = 1 there are no edges: op_gain_solve.
+int op_gain_block_solve(int n, int bx, int by, const int64_t* count, const int64_t* sums, double sigma_n, double sigma_g, double sigma_s,
+		int per_channel, float* gains) {
+	if (n < 1 || !gains || (n > 1 && (!count || !sums)) || bx < 1 || bx > GAIN_MAX_BLOCKS || by < 1 || by > GAIN_MAX_BLOCKS ||
+			!(sigma_n > 0) || !(sigma_g > 0) || !(sigma_s > 0) || !std::isfinite(sigma_n) || !std::isfinite(sigma_g) || !std::isfinite(sigma_s) ||
+			(per_channel != 0 && per_channel != 1))
+		OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: bad argument");
+	const long long B = (long long)bx * by, entries = (long long)n * (n - 1) / 2 * B * B;
+	if (n * B > GAIN_BLOCK_MAX_UNKNOWNS)
+		OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_solve: " + std::to_string(n * B) + " units (n bx by) exceed the dense solve's " +
+		        std::to_string(GAIN_BLOCK_MAX_UNKNOWNS));
+	for (long long e = 0; e < entries; ++e)
+		if (count[e] < 0) OP_FAIL(OP_ERR_INVALID, "op_gain_block_solve: negative overlap count at entry " + std::to_string(e));
+	return gain_unit_solve("op_gain_block_solve", n, bx, by, count, sums, sigma_n, sigma_g, sigma_s, per_channel, gains);
 }
 
 // Vignetting compensation, host only: gains g_k and one curve a = (1, a1, a2, a3) shared by all views minimising
@@ -1776,24 +1646,21 @@ int op_vignette_solve(int n, const int64_t* count, const int64_t* moments, int d
 		if (count[p] < 0) OP_FAIL(OP_ERR_INVALID, "op_vignette_solve: negative overlap count at pair " + std::to_string(p));
 	for (int e = 0; e < 3 * n; ++e) gains[e] = 1.f;
 	poly[0] = poly[1] = poly[2] = 0.f;
-	// the pairs with overlap, in pair order, with their moments in [0, 1] units; the active images as op_gain_solve's
+	// the pairs with overlap, in pair order, with their moments in [0, 1] units, and the active images
 	struct VPair { int a, b; double N, A[7], B[7], C[16]; };
 	std::vector<VPair> pairs;
-	std::vector<int> slot(n, -1), act;
 	double Mtot = 0.0;
-	for (int a = 0; a < n; ++a)
-		for (int b = a + 1; b < n; ++b) {
-			const long long p = (long long)a * n - (long long)a * (a + 1) / 2 + (b - a - 1);
-			if (count[p] <= 0) continue;
-			VPair v; v.a = a; v.b = b; v.N = (double)count[p];
-			const int64_t* m = moments + (long long)VIG_MOMENTS * p;
-			for (int k = 0; k < 7; ++k) { v.A[k] = (double)m[k] / GAIN_FIX; v.B[k] = (double)m[7 + k] / GAIN_FIX; }
-			for (int k = 0; k < 16; ++k) v.C[k] = (double)m[14 + k] / GAIN_FIX;
-			pairs.push_back(v);
-			slot[a] = slot[b] = 0;
-			Mtot += v.N;
-		}
-	for (int a = 0; a < n; ++a) if (slot[a] == 0) { slot[a] = (int)act.size(); act.push_back(a); }
+	std::vector<int> slot;
+	const std::vector<int> act = active_images(n, slot, [&](int a, int b, long long p) {
+		if (count[p] <= 0) return false;
+		VPair v; v.a = a; v.b = b; v.N = (double)count[p];
+		const int64_t* mo = moments + (long long)VIG_MOMENTS * p;
+		for (int k = 0; k < 7; ++k) { v.A[k] = (double)mo[k] / GAIN_FIX; v.B[k] = (double)mo[7 + k] / GAIN_FIX; }
+		for (int k = 0; k < 16; ++k) v.C[k] = (double)mo[14 + k] / GAIN_FIX;
+		pairs.push_back(v);
+		Mtot += v.N;
+		return true;
+	});
 	const int m = (int)act.size();
 	if (m == 0) return OP_OK;
 	const double inv_n2 = 1.0 / (sigma_n * sigma_n), inv_g2 = 1.0 / (sigma_g * sigma_g), inv_v2 = 1.0 / (sigma_v * sigma_v);
