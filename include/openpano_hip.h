@@ -301,6 +301,8 @@ int op_pairwise_table(op_ctx* ctx, const op_features* f, const op_matches* m, co
  * Threading: the tables are cached per context -- geometry key + host and device copy, (2 W + H) doubles each, for the
  * context's lifetime).  Like every other per-context workspace they make an op_ctx THREAD-COMPATIBLE, not thread-safe:
  * one call at a time per context; concurrent callers use one context each (as the adapters in pano_hip.hh do).
+ * Multiband: a cfg->MULTIBAND / cfg->GAUSS_WINDOW_FACTOR whose blur at some level is wider than 31 taps (GaussCache's
+ * half-width above 15: wf at levels 0-2, 1.5 wf at 3-8, 2 wf at 9) returns OP_ERR_UNSUPPORTED, before any device work.
  * ===================================================================================== */
 typedef struct op_blend_image {
 	const float* data;    /* H x W x 3 fp32 (ImageRef::img, stitch/imageref.hh:15-17) */

@@ -1201,6 +1201,14 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 		int gbx, int gby, const char* who, op_canvas** out) {
 	int rc = check_blend_args(who, g);
 	if (rc != OP_OK) return rc;
+	// multiband: the blur of every level but the last (GaussCache), checked before any allocation or launch -- a refusal
+	// after them would hand blocks still being written back to the process-wide pool, which does not track streams
+	std::vector<BlurTaps> level_taps(cfg->MULTIBAND > 1 ? cfg->MULTIBAND - 1 : 0);
+	for (int level = 0; level < (int)level_taps.size(); ++level) {
+		memset(&level_taps[level], 0, sizeof(BlurTaps));
+		if (gauss_taps((float)(std::sqrt(level * 2 + 1.0) * 4), cfg->GAUSS_WINDOW_FACTOR, level_taps[level]) != 0)
+			OP_FAIL(OP_ERR_UNSUPPORTED, std::string(who) + ": Gaussian kernel wider than 31 taps");
+	}
 	HIPCHK(hipSetDevice(ctx->device));
 	hipStream_t st = ctx->stream;
 	int H, W;
@@ -1266,10 +1274,7 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 			bool band_done = false;
 			if (!is_last) {
 				ProfScope ps(ctx, "multiband blur");
-				BlurTaps taps; memset(&taps, 0, sizeof(taps));
-				if (gauss_taps((float)(std::sqrt(level * 2 + 1.0) * 4), cfg->GAUSS_WINDOW_FACTOR, taps) != 0) {
-					pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_UNSUPPORTED, std::string(who) + ": Gaussian kernel wider than 31 taps");
-				}
+				const BlurTaps& taps = level_taps[level];
 				if (taps.center == 6 || taps.center == 9) {       // shipped GAUSS_WINDOW_FACTOR: both passes in one kernel
 					const int C = taps.center, two = 256 - 2 * C, segr = (C <= 6 ? 8 : 6) * (2 * C + 2);      // k_mb_blur_fused: SEG
 					unsigned items = 1;

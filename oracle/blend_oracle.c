@@ -185,8 +185,53 @@ static int interpolate(const float* img, int rows, int cols, float r, float c, f
 	return 1;
 }
 
-/* GET_COLOR_AND_W (blender.cc:26-36); returns 0 for "continue" */
-static int color_and_w(const orc_blend_geom* g, const orc_blend_image* im, int i, int j, int ordered_input,
+/* ---- exposure gains of the device blend (include/openpano_hip.h: op_blend_gains, op_blend_block_gains,
+ * op_blend_vignette), an extension beyond the reference.  mode: ORC_GAIN_NONE / IMAGE / BLOCK / VIGNETTE; the table in
+ * the layout of that entry point: n x 3; n x gby x gbx x 3; n x 3 then the curve's a1..a3.  The header's fp32
+ * expressions, in its order; a channel whose gain is exactly 1 is left as it is. ---- */
+typedef struct { int mode; const float* table; int gbx, gby, n; } orc_gain;
+
+static void gain_channel(float* col, float g) { if (g != 1.f) *col = fminf(*col * g, 1.f); }
+
+/* one axis of the block-centre interpolation */
+static void gain_block_axis(float x, int nb, int dim, int* i0, int* i1, float* t) {
+	const float f = x * (float)nb / (float)dim - 0.5f;
+	int a = (int)floorf(f);
+	a = a < 0 ? 0 : (a > nb - 1 ? nb - 1 : a);
+	*i0 = a; *i1 = a + 1 < nb ? a + 1 : nb - 1;
+	const float tt = f - (float)a;
+	*t = tt < 0.f ? 0.f : (tt > 1.f ? 1.f : tt);
+}
+
+/* the gain of image k (ImageRef size w x h) on its valid sample col, interpolated at image coordinates (r, c) */
+static void apply_gain(const orc_gain* G, int k, int w, int h, float r, float c, float col[3]) {
+	if (G->mode == ORC_GAIN_IMAGE) {
+		for (int ch = 0; ch < 3; ++ch) gain_channel(&col[ch], G->table[3 * (size_t)k + ch]);
+	} else if (G->mode == ORC_GAIN_BLOCK) {
+		const int bx = G->gbx, by = G->gby;
+		const float* T = G->table + (size_t)3 * k * bx * by;
+		int u0, u1, v0, v1; float tx, ty;
+		gain_block_axis(c, bx, w, &u0, &u1, &tx);
+		gain_block_axis(r, by, h, &v0, &v1, &ty);
+		for (int ch = 0; ch < 3; ++ch) {
+			const float g00 = T[(v0 * bx + u0) * 3 + ch], g01 = T[(v0 * bx + u1) * 3 + ch];
+			const float g10 = T[(v1 * bx + u0) * 3 + ch], g11 = T[(v1 * bx + u1) * 3 + ch];
+			const float top = g00 + tx * (g01 - g00), bot = g10 + tx * (g11 - g10);
+			gain_channel(&col[ch], top + ty * (bot - top));
+		}
+	} else if (G->mode == ORC_GAIN_VIGNETTE) {
+		const float* poly = G->table + 3 * (size_t)G->n;
+		const float fw = (float)w, fh = (float)h;
+		const float dx = c - 0.5f * fw, dy = r - 0.5f * fh;
+		const float rho = fminf((dx * dx + dy * dy) / (0.25f * (fw * fw + fh * fh)), 1.f);
+		const float V = 1.f + rho * (poly[0] + rho * (poly[1] + rho * poly[2]));
+		for (int ch = 0; ch < 3; ++ch) gain_channel(&col[ch], G->table[3 * (size_t)k + ch] / V);
+	}
+}
+
+/* GET_COLOR_AND_W (blender.cc:26-36) of image k, its valid sample gained before the weight multiplication; returns 0
+ * for "continue" */
+static int color_and_w(const orc_blend_geom* g, const orc_blend_image* im, int k, const orc_gain* G, int i, int j, int ordered_input,
 		float color[3], float* w_out) {
 	double ic[2];
 	canvas_to_image(g, im, j, i, ic);
@@ -195,6 +240,7 @@ static int color_and_w(const orc_blend_geom* g, const orc_blend_image* im, int i
 	float r = (float)ic[1], c = (float)ic[0];
 	if (!interpolate(im->data, im->h, im->w, r, c, color)) return 0;
 	if (color[0] < 0) return 0;
+	apply_gain(G, k, im->w, im->h, r, c, color);
 	float w = (float)(0.5 - fabs(c / im->w - 0.5));
 	if (!ordered_input) w = (float)(w * (0.5 - fabs(r / im->h - 0.5)));
 	color[0] *= w; color[1] *= w; color[2] *= w;
@@ -202,7 +248,9 @@ static int color_and_w(const orc_blend_geom* g, const orc_blend_image* im, int i
 	return 1;
 }
 
-int orc_blend_linear(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int ordered_input, int lazy_read, float* out) {
+int orc_blend_linear_gained(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int ordered_input, int lazy_read,
+		int gain_mode, const float* gains, int gbx, int gby, float* out) {
+	const orc_gain G = {gain_mode, gains, gbx, gby, n};
 	int H, W; orc_blend_dims(g, imgs, n, &H, &W);
 	int* roi = (int*)malloc(sizeof(int) * 4 * n);
 	for (int k = 0; k < n; ++k) roi_of(g, imgs[k].range, roi + 4 * k);
@@ -213,7 +261,7 @@ int orc_blend_linear(const orc_blend_geom* g, const orc_blend_image* imgs, int n
 			const int* q = roi + 4 * k;
 			for (int i = q[1]; i < q[3]; ++i) for (int j = q[0]; j < q[2]; ++j) {
 				float color[3], w;
-				if (!color_and_w(g, &imgs[k], i, j, ordered_input, color, &w)) continue;
+				if (!color_and_w(g, &imgs[k], k, &G, i, j, ordered_input, color, &w)) continue;
 				float* row = out + ((size_t)i * W + j) * 3;
 				row[0] += color[0]; row[1] += color[1]; row[2] += color[2];
 				weight[(size_t)i * W + j] += w;
@@ -232,7 +280,7 @@ int orc_blend_linear(const orc_blend_geom* g, const orc_blend_image* imgs, int n
 				const int* q = roi + 4 * k;
 				if (!(i >= q[1] && i <= q[3] && j >= q[0] && j <= q[2])) continue;	/* Range::contain, inclusive */
 				float color[3], w;
-				if (!color_and_w(g, &imgs[k], i, j, ordered_input, color, &w)) continue;
+				if (!color_and_w(g, &imgs[k], k, &G, i, j, ordered_input, color, &w)) continue;
 				isum[0] += color[0]; isum[1] += color[1]; isum[2] += color[2];
 				wsum += w;
 			}
@@ -245,6 +293,10 @@ int orc_blend_linear(const orc_blend_geom* g, const orc_blend_image* imgs, int n
 	}
 	free(roi);
 	return 0;
+}
+
+int orc_blend_linear(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int ordered_input, int lazy_read, float* out) {
+	return orc_blend_linear_gained(g, imgs, n, ordered_input, lazy_read, ORC_GAIN_NONE, NULL, 0, 0, out);
 }
 
 /* ---- multi-band ---- */
@@ -306,7 +358,9 @@ static void blur_wpix(const wpix* img, wpix* ret, int h, int w, const float* kbu
 	free(mem);
 }
 
-int orc_blend_multiband(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int band_level, int window_factor, float* out) {
+int orc_blend_multiband_gained(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int band_level, int window_factor,
+		int gain_mode, const float* gains, int gbx, int gby, float* out) {
+	const orc_gain G = {gain_mode, gains, gbx, gby, n};
 	int H, W; orc_blend_dims(g, imgs, n, &H, &W);
 	int* roi = (int*)malloc(sizeof(int) * 4 * n);
 	wpix** cur = (wpix**)calloc(n, sizeof(wpix*));
@@ -329,7 +383,8 @@ int orc_blend_multiband(const orc_blend_geom* g, const orc_blend_image* imgs, in
 			if (!ok) {
 				px->w = 0; px->c[0] = px->c[1] = px->c[2] = 0;
 				mask[k][(size_t)i * rw + j] = 1;
-			} else {
+			} else {		/* the gain reaches every valid ROI pixel, also those one past the target */
+				apply_gain(&G, k, imgs[k].w, imgs[k].h, (float)oc[1], (float)oc[0], c);
 				px->c[0] = c[0]; px->c[1] = c[1]; px->c[2] = c[2];
 				oc[0] = oc[0] / imgs[k].w - 0.5;
 				oc[1] = oc[1] / imgs[k].h - 0.5;
@@ -397,6 +452,10 @@ int orc_blend_multiband(const orc_blend_geom* g, const orc_blend_image* imgs, in
 	for (int k = 0; k < n; ++k) { free(cur[k]); free(nxt[k]); free(mask[k]); }
 	free(cur); free(nxt); free(mask); free(roi); free(tmask);
 	return 0;
+}
+
+int orc_blend_multiband(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int band_level, int window_factor, float* out) {
+	return orc_blend_multiband_gained(g, imgs, n, band_level, window_factor, ORC_GAIN_NONE, NULL, 0, 0, out);
 }
 
 /* ---- CylinderWarper::get_projector + CylinderProject::project (stitch/warp.cc:13-75) ---- */

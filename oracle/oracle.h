@@ -108,6 +108,19 @@ int orc_blend_prepare(int proj_method, int identity_idx, int n, const int* shape
 int orc_blend_dims(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int* h, int* w);
 int orc_blend_linear(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int ordered_input, int lazy_read, float* out);
 int orc_blend_multiband(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int band_level, int window_factor, float* out);
+/* The two blenders with the exposure gains of the device blend (an extension beyond the reference; include/openpano_hip.h:
+ * op_blend_gains, op_blend_block_gains, op_blend_vignette) on every valid sample -- in the linear blender before the
+ * weight multiplication, in the multiband blender on every ROI pixel of level 0 (also those one past the target).
+ * gain_mode and the layout of gains (gbx / gby are read by ORC_GAIN_BLOCK only):
+ *   ORC_GAIN_NONE      no table: the two functions above
+ *   ORC_GAIN_IMAGE     n x 3
+ *   ORC_GAIN_BLOCK     n x gby x gbx x 3
+ *   ORC_GAIN_VIGNETTE  n x 3, then the shared curve's a1, a2, a3 */
+enum { ORC_GAIN_NONE = 0, ORC_GAIN_IMAGE = 1, ORC_GAIN_BLOCK = 2, ORC_GAIN_VIGNETTE = 3 };
+int orc_blend_linear_gained(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int ordered_input, int lazy_read,
+		int gain_mode, const float* gains, int gbx, int gby, float* out);
+int orc_blend_multiband_gained(const orc_blend_geom* g, const orc_blend_image* imgs, int n, int band_level, int window_factor,
+		int gain_mode, const float* gains, int gbx, int gby, float* out);
 /* CylinderWarper::warp (stitch/warp.hh:47-55, warp.cc:25-75): shape/keypoints, then pixels */
 int orc_cyl_shape(int w, int h, double h_factor, float focal_length, double* pts, int npts,
 		int* new_w, int* new_h, double* offset);

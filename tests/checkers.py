@@ -136,6 +136,31 @@ class _StagedBase:
         return st
 
 
+GAIN_NONE, GAIN_IMAGE, GAIN_BLOCK, GAIN_VIGNETTE = 0, 1, 2, 3      # oracle.h: ORC_GAIN_*
+
+
+def gain_table(n, gains=None, vignette=None):
+    """(mode, float32 table or None, gbx, gby) of orc_blend_*_gained for the gains / vignette hip.BlendCall accepts"""
+    g = None if gains is None else np.asarray(gains, np.float32)
+    if g is not None and g.ndim == 4:
+        if vignette is not None or g.shape[0] != n or g.shape[3] != 3:
+            raise ValueError(f"block gains must be ({n}, by, bx, 3) without a curve, got {g.shape}")
+        return GAIN_BLOCK, np.ascontiguousarray(g.reshape(-1)), int(g.shape[2]), int(g.shape[1])
+    if g is not None:
+        g = np.repeat(g.reshape(n, 1), 3, axis=1) if g.size == n else g
+        if g.shape != (n, 3):
+            raise ValueError(f"gains must be ({n}, 3) or ({n},), got {g.shape}")
+    if vignette is not None:
+        a = np.asarray(vignette, np.float32).reshape(-1)
+        if a.shape != (3,):
+            raise ValueError(f"vignette must hold a1, a2, a3, got {a.shape}")
+        g = np.ones((n, 3), np.float32) if g is None else g
+        return GAIN_VIGNETTE, np.ascontiguousarray(np.concatenate([g.reshape(-1), a]), np.float32), 0, 0
+    if g is None:
+        return GAIN_NONE, None, 0, 0
+    return GAIN_IMAGE, np.ascontiguousarray(g.reshape(-1), np.float32), 0, 0
+
+
 class Oracle(_StagedBase):
     prefix = "orc_"
 
@@ -172,6 +197,8 @@ class Oracle(_StagedBase):
         lib.orc_blend_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.orc_blend_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p]
         lib.orc_blend_multiband.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p]
+        lib.orc_blend_linear_gained.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, _f32p]
+        lib.orc_blend_multiband_gained.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, _f32p]
         lib.orc_cyl_shape.argtypes = [C.c_int, C.c_int, C.c_double, C.c_float, _f64p, C.c_int,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), _f64p]
         lib.orc_cyl_project.argtypes = [_f32p, C.c_int, C.c_int, C.c_double, C.c_float, _f32p]
@@ -179,9 +206,28 @@ class Oracle(_StagedBase):
     def _cp(self):
         return C.byref(self.ccfg)
 
-    def blend(self, imgs, homos, proj_method, identity_idx, cfg=None):
+    def blend(self, imgs, homos, proj_method, identity_idx, cfg=None, gains=None, vignette=None):
         """ConnectedImages::blend over in-memory images. homos: n x 3 x 3 (ImageComponent::homo).
+        gains / vignette as hip.BlendCall takes them: (n, 3) or (n,) per-image gains, (n, by, bx, 3) block gains, and
+        vignette = (a1, a2, a3) with per-image gains or None (= 1): the device blend's gain modes (orc_blend_*_gained).
         -> (canvas (H, W, 3) f32, meta dict(geom(6), ranges (n,4), homo_inv (n,9)))"""
+        cfg = cfg or self.cfg
+        n = len(imgs)
+        mode, table, gbx, gby = gain_table(n, gains, vignette)
+        geom, arr, _keep, (h, w), meta = self.blend_inputs(imgs, homos, proj_method, identity_idx, cfg)
+        out = np.empty((h, w, 3), np.float32)
+        tp = None if table is None else table.ctypes.data_as(C.c_void_p)
+        if cfg.MULTIBAND > 0:
+            self.lib.orc_blend_multiband_gained(C.byref(geom), arr, n, int(cfg.MULTIBAND), int(cfg.GAUSS_WINDOW_FACTOR),
+                                                mode, tp, gbx, gby, out.reshape(-1))
+        else:
+            self.lib.orc_blend_linear_gained(C.byref(geom), arr, n, int(cfg.ORDERED_INPUT), int(cfg.LAZY_READ),
+                                             mode, tp, gbx, gby, out.reshape(-1))
+        return out, meta
+
+    def blend_inputs(self, imgs, homos, proj_method, identity_idx, cfg=None):
+        """orc_blend_prepare + the image array of ConnectedImages::blend -> (OrcBlendGeom, OrcBlendImage array, the
+        contiguous images it points into (keep them alive), canvas (H, W), meta as blend() returns it)"""
         cfg = cfg or self.cfg
         n = len(imgs)
         imgs = [np.ascontiguousarray(im, np.float32) for im in imgs]
@@ -200,14 +246,9 @@ class Oracle(_StagedBase):
                 arr[i].range[k] = ranges[i, k]
         h, w = C.c_int(), C.c_int()
         self.lib.orc_blend_dims(C.byref(geom), arr, n, C.byref(h), C.byref(w))
-        out = np.empty((h.value, w.value, 3), np.float32)
-        if cfg.MULTIBAND > 0:
-            self.lib.orc_blend_multiband(C.byref(geom), arr, n, int(cfg.MULTIBAND), int(cfg.GAUSS_WINDOW_FACTOR), out.reshape(-1))
-        else:
-            self.lib.orc_blend_linear(C.byref(geom), arr, n, int(cfg.ORDERED_INPUT), int(cfg.LAZY_READ), out.reshape(-1))
         meta = dict(geom=np.array([geom.proj_min[0], geom.proj_min[1], geom.proj_max[0], geom.proj_max[1],
                                    geom.resolution[0], geom.resolution[1]]), ranges=ranges, homo_inv=hinv)
-        return out, meta
+        return geom, arr, imgs, (h.value, w.value), meta
 
     def crop(self, mat):
         """crop(mat) (lib/imgproc.cc:200-235) -> cropped array (view semantics: a copy)"""

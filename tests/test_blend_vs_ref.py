@@ -22,6 +22,13 @@ CASES = [
     ("camera", 2, dict(MULTIBAND=3)),
     ("flat", 0, dict(ESTIMATE_CAMERA=0, TRANS=1, ORDERED_INPUT=1, MULTIBAND=5)),
     ("camera", 2, dict(MULTIBAND=1)),
+    # level counts and window factors that reach every multiband kernel path of the device (test_gpu_blend_paths.py):
+    # per-level half-widths wf (levels 0-2), floor(1.5 wf) (3-8); factor 10 reaches 15, the widest the device takes
+    ("flat", 0, dict(ESTIMATE_CAMERA=0, TRANS=1, ORDERED_INPUT=1, MULTIBAND=6)),
+    ("flat", 0, dict(ESTIMATE_CAMERA=0, TRANS=1, ORDERED_INPUT=1, MULTIBAND=6, GAUSS_WINDOW_FACTOR=4)),
+    ("camera", 2, dict(MULTIBAND=5, GAUSS_WINDOW_FACTOR=9)),
+    ("camera", 1, dict(ESTIMATE_CAMERA=0, CYLINDER=1, ORDERED_INPUT=1, MULTIBAND=7, GAUSS_WINDOW_FACTOR=10)),
+    ("camera", 2, dict(MULTIBAND=7, GAUSS_WINDOW_FACTOR=4)),
 ]
 
 
@@ -32,7 +39,10 @@ def test_blend_oracle_equals_reference(ref, proj, method, over):
     views, homos = synth.pano_scene(4, 120, 160, seed=5 + method, proj=proj)
     ref.set_config(**{k: v for k, v in cfg.raw_items()})
     ref.lib.ref_set_threads(1)
-    want, wmeta = ref.blend(views, homos, method, 2)
+    try:
+        want, wmeta = ref.blend(views, homos, method, 2)
+    finally:                                 # the window factor is the SIFT's too: later tests expect the shipped one
+        ref.set_config(GAUSS_WINDOW_FACTOR=PanoConfig().GAUSS_WINDOW_FACTOR)
     got, gmeta = Oracle(cfg).blend(views, homos, method, 2, cfg)
     assert want.shape == got.shape and want.shape[0] > 50 and want.shape[1] > 200
     for k in ("geom", "ranges", "homo_inv"):
