@@ -461,6 +461,28 @@ int op_vignette_solve(int n, const int64_t* count, const int64_t* moments, int d
 int op_blend_vignette(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, const float* gains,
 		const float* poly, op_canvas** out);
 
+/* ---- PNG OUTPUT (ABI 12) -- replaces write_rgb(fname, mat) and the encoder behind it, write_png -> lodepng::encode
+ * (lib/imgio.cc:25-41,98-113; called by main.cc:226-233), the largest single cost of a whole run of the reference's CLI.
+ * The canvas is quantised, filtered, deflated and framed on the device; one D2H brings back the finished file.
+ * Format: 8-bit RGB (colour type 2), no interlace, no ancillary chunks: signature, IHDR, IDAT chunks, IEND.  The pixels are
+ * op_canvas_copy_u8's bytes (Color::NO -> 255, v * 255 truncated); the reference hands lodepng RGBA with alpha 255, which
+ * lodepng's colour reduction stores as RGB, so a decoder sees the same pixels from both files.  The IDAT payload is one zlib
+ * stream; the file is a function of the pixels alone (bit-equal between runs, contexts and devices): DESIGN.md section 11
+ * gives the parse and the Huffman construction, tests/harness/png_ref.c restates them serially.
+ * op_canvas_encode_png: the device-resident canvas of op_blend / op_canvas_crop.  An empty canvas (h = 0 or w = 0, which
+ * op_canvas_crop can return) is OP_ERR_INVALID: the format has no zero-sized image.  (lib/imgio.cc:25-41,98-113)
+ * op_png_encode_u8: the same encoder for H x W x 3 bytes in host memory -- what the reference's main.cc holds after
+ * write_rgb's quantisation loop (lib/imgio.cc:25-41,98-113).
+ * op_png_size / op_png_copy: the file's length and its bytes (host must have room for op_png_size bytes; lib/imgio.cc:98-113
+ * hands them to lodepng's file writer).  op_png_free releases the object.  Filtered streams above 4 GiB: OP_ERR_UNSUPPORTED.
+ * Threading and ownership as op_blend: one call at a time per context; the caller owns the returned op_png. */
+typedef struct op_png op_png;
+int op_canvas_encode_png(op_ctx* ctx, const op_canvas* c, op_png** out);
+int op_png_encode_u8(op_ctx* ctx, const unsigned char* rgb_host, int h, int w, op_png** out);
+int64_t op_png_size(const op_png* p);
+int op_png_copy(op_ctx* ctx, const op_png* p, unsigned char* host);
+void op_png_free(op_png* p);
+
 /* CYLINDER mode pre-warp -- replaces CylinderWarper::warp (stitch/warp.hh:47-55, warp.cc:13-75).
  * op_cyl_warp_shape is the host part (projector, output shape, offset and the keypoints, which
  * are centred coordinates updated in place: warp.cc:46-67); op_cyl_warp renders the pixels. */

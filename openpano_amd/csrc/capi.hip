@@ -144,7 +144,7 @@ int op_ctx_profile_get(op_ctx* c, int i, const char** label, double* total_ms, l
 }
 
 const char* op_last_error(void) { return g_last_error.c_str(); }
-int op_abi_version(void) { return 11; }     // 11: op_vignette_overlap, op_vignette_solve, op_blend_vignette; 10: op_gain_block_overlap, op_gain_block_solve, op_blend_block_gains; 9: op_gain_overlap, op_gain_solve, op_blend_gains; 8: op_matches_concat; 3: op_blend_image.mat_h / mat_w; 4: resident match lists, op_sift_batch_host, op_ransac_pairs_multi; 5: op_ctx_profile_only; 6: op_debug_set_desc_list_cap; 7: op_pairwise_table
+int op_abi_version(void) { return 12; }     // 12: op_canvas_encode_png, op_png_encode_u8, op_png_size, op_png_copy, op_png_free; 11: op_vignette_overlap, op_vignette_solve, op_blend_vignette; 10: op_gain_block_overlap, op_gain_block_solve, op_blend_block_gains; 9: op_gain_overlap, op_gain_solve, op_blend_gains; 8: op_matches_concat; 3: op_blend_image.mat_h / mat_w; 4: resident match lists, op_sift_batch_host, op_ransac_pairs_multi; 5: op_ctx_profile_only; 6: op_debug_set_desc_list_cap; 7: op_pairwise_table
 
 void op_config_default(op_config* c) {
 	// src/config.cfg (every literal goes through a float, lib/config.cc:19-26)

@@ -218,6 +218,13 @@ def lib():
                                         C.c_void_p]
         L.op_blend_vignette.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    if hasattr(L, "op_canvas_encode_png"):
+        L.op_canvas_encode_png.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.op_png_encode_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.op_png_size.restype = C.c_int64
+        L.op_png_size.argtypes = [C.c_void_p]
+        L.op_png_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.op_png_free.argtypes = [C.c_void_p]
     L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
@@ -773,6 +780,17 @@ class Canvas:
         check(lib().op_canvas_copy_u8(self.ctx.handle, self.handle, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def png_bytes(self) -> bytes:
+        """the canvas as a PNG file (8-bit RGB, numpy_u8()'s pixels), encoded on the device (op_canvas_encode_png)"""
+        h = C.c_void_p()
+        check(lib().op_canvas_encode_png(self.ctx.handle, self.handle, C.byref(h)))
+        return _take_png(self.ctx, h)
+
+    def write_png(self, path):
+        data = self.png_bytes()
+        with open(path, "wb") as f:
+            f.write(data)
+
     def free(self):
         if self.handle:
             lib().op_canvas_free(self.handle); self.handle = None
@@ -782,6 +800,25 @@ class Canvas:
             self.free()
         except Exception:
             pass
+
+
+def _take_png(ctx: Context, handle) -> bytes:
+    try:
+        out = np.empty(lib().op_png_size(handle), np.uint8)
+        check(lib().op_png_copy(ctx.handle, handle, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()
+    finally:
+        lib().op_png_free(handle)
+
+
+def encode_png_u8(ctx: Context, array) -> bytes:
+    """PNG file of an (H, W, 3) uint8 array in host memory, through the device encoder (op_png_encode_u8)"""
+    a = np.ascontiguousarray(array, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"encode_png_u8: expected (H, W, 3) bytes, got {a.shape}")
+    h = C.c_void_p()
+    check(lib().op_png_encode_u8(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], C.byref(h)))
+    return _take_png(ctx, h)
 
 
 def blend_prepare(cfg, shapes_wh, homos, proj_method, identity_idx):

@@ -735,6 +735,36 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 template <typename Bundle>
 inline Mat32f hip_blend(const Bundle& b, bool crop = false) { return hip_blend(b, crop, std::vector<float>()); }
 
+// ---- write_rgb(fname, mat) for a .png name (lib/imgio.cc:25-41,98-113; main.cc:226-233): the file is encoded on the device
+// (op_canvas_encode_png / op_png_encode_u8) instead of by lodepng on one host thread.  Same pixels as the reference's file
+// (Color::NO -> white, v * 255 truncated), 8-bit RGB where lodepng is handed RGBA with alpha 255 and reduces it to RGB.
+inline void hip_write_png_file(const char* fname, op_png* png) {
+	std::vector<unsigned char> bytes((size_t)op_png_size(png));
+	PANO_HIP_CHECK(op_png_copy(HipContext::get(), png, bytes.data()));
+	op_png_free(png);
+	FILE* f = fopen(fname, "wb");
+	if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
+		fprintf(stderr, "hip_write_png: cannot write %s\n", fname);
+		exit(1);
+	}
+}
+// the device canvas a blend left behind (op_blend*, op_canvas_crop): the fp32 canvas does not come back at all
+inline void hip_write_png(const char* fname, const op_canvas* canvas) {
+	op_png* png = nullptr;
+	PANO_HIP_CHECK(op_canvas_encode_png(HipContext::get(), canvas, &png));
+	hip_write_png_file(fname, png);
+}
+// write_rgb's signature: a matrix in host memory, quantised here exactly as write_png does (lib/imgio.cc:30-36)
+inline void hip_write_png(const char* fname, const Mat32f& mat) {
+	const size_t n = (size_t)mat.rows() * mat.cols() * 3;
+	std::vector<unsigned char> rgb(n);
+	const float* p = mat.ptr();
+	for (size_t i = 0; i < n; ++i) rgb[i] = (unsigned char)((p[i] < 0 ? 1 : p[i]) * 255);
+	op_png* png = nullptr;
+	PANO_HIP_CHECK(op_png_encode_u8(HipContext::get(), rgb.data(), mat.rows(), mat.cols(), &png));
+	hip_write_png_file(fname, png);
+}
+
 #ifndef OPENPANO_WITH_REFERENCE
 inline void ConnectedImages::prepare(bool set_inverse, bool set_range) {
 	std::vector<double> hinv, ranges;

@@ -21,6 +21,8 @@
 // --vignetting (anywhere; not with --gain-blocks): grey gains plus one radial falloff curve shared by all views
 // (HipStitcher::vignetting, hip_vignette_compensate); out.bin then ends with n*3 f32 gains and the curve's 3 f32
 // coefficients a1, a2, a3, where --gain-compensation puts its gains.
+// --png PATH (anywhere): additionally writes the panorama out.bin holds as an 8-bit RGB PNG, encoded on the device
+// (hip_write_png: write_rgb's quantisation, lib/imgio.cc:25-41); out.bin is the same with and without it.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
@@ -81,7 +83,7 @@ static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::
 // Stitcher::build() under ESTIMATE_CAMERA (stitch/stitcher.cc:32-64), stage by stage so that every
 // intermediate can be written out
 static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby,
-		bool vig) {
+		bool vig, const char* png_path) {
 	Stitcher st(mats, base_seed);
 	FILE* fo = fopen(out_path, "wb");
 	if (!fo) { perror(out_path); return 2; }
@@ -116,6 +118,7 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
 	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
+	if (png_path) hip_write_png(png_path, pano);
 	if (gain || vig) {
 		put(fo, st.gains.data(), st.gains.size());
 		const size_t per = st.gains.size() / n;      // 3 per image, or 3 per block
@@ -130,7 +133,8 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 }
 
 // Stitcher::build() as a client calls it, gain compensation per HipStitcher::gain_compensation
-static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain, int gbx, int gby, bool vig) {
+static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain, int gbx, int gby, bool vig,
+		const char* png_path) {
 	Stitcher st(mats, base_seed);
 	st.gain_compensation = gain;
 	st.vignetting = vig;
@@ -143,6 +147,7 @@ static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint
 	put(fo, st.gains.data(), st.gains.size());
 	if (vig) put(fo, st.vignette_poly.data(), 3);
 	fclose(fo);
+	if (png_path) hip_write_png(png_path, pano);
 	fprintf(stderr, "Final Image Size: (%d, %d), %zu gains\n", pano.cols(), pano.rows(), st.gains.size());
 	return 0;
 }
@@ -151,11 +156,13 @@ int main(int argc, char** argv) {
 	bool gain = false;
 	int gbx = 1, gby = 1;
 	bool vig = false;
+	const char* png_path = nullptr;
 	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
 			if (std::string(argv[k]) == "--gain-compensation") gain = true;
 			else if (std::string(argv[k]) == "--vignetting") vig = true;
+			else if (std::string(argv[k]) == "--png" && k + 1 < argc) png_path = argv[++k];
 			else if (std::string(argv[k]) == "--gain-blocks" && k + 1 < argc) {
 				if (sscanf(argv[++k], "%dx%d", &gbx, &gby) != 2 || gbx < 1 || gbx > 16 || gby < 1 || gby > 16) {
 					fprintf(stderr, "--gain-blocks wants BXxBY, each in [1, 16]; got %s\n", argv[k]); return 2;
@@ -167,7 +174,7 @@ int main(int argc, char** argv) {
 		argc = m;
 	}
 	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH]\n", argv[0]); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
@@ -184,8 +191,8 @@ int main(int argc, char** argv) {
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
-	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby, vig);
-	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig);
+	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby, vig, png_path);
+	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path);
 
 	// ---- StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27)
 	std::vector<ImageRef> imgs;
@@ -261,6 +268,7 @@ int main(int argc, char** argv) {
 		put(fo, gains.data(), gains.size());
 		if (vig) put(fo, poly.data(), 3);
 		fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
+		if (png_path) hip_write_png(png_path, pano);
 	} else {
 		put1<int32_t>(fo, 0); put1<int32_t>(fo, 0);
 	}
