@@ -24,6 +24,21 @@
 #define PNG_SLOT (PNG_SEG + 16)   // worst case of a segment's deflate bytes (stored: SEG + 5), 16-byte aligned
 #define PNG_ADLER 65521u
 #define PNG_HEAD_BYTES 47    // signature 8, IHDR chunk 25, zlib-header chunk 14
+// Code-length limits of the three Huffman alphabets.  The defaults are deflate's own; RFC 1951 bounds code lengths from above
+// only, so a tighter limit still gives a valid file -- the tests build a variant with 11 / 11 / 5 to run huff_build's Kraft
+// fix-up on ordinary inputs (tests/test_gpu_png_variant.py; tests/harness/png_ref.c has the same knobs).
+#ifndef OP_PNG_LIT_MAXBITS
+#define OP_PNG_LIT_MAXBITS 15
+#endif
+#ifndef OP_PNG_DIST_MAXBITS
+#define OP_PNG_DIST_MAXBITS 15
+#endif
+#ifndef OP_PNG_CL_MAXBITS
+#define OP_PNG_CL_MAXBITS 7
+#endif
+static_assert(OP_PNG_LIT_MAXBITS >= 9 && OP_PNG_LIT_MAXBITS <= 15, "286 codes need 9 bits; deflate allows 15");
+static_assert(OP_PNG_DIST_MAXBITS >= 5 && OP_PNG_DIST_MAXBITS <= 15, "30 codes need 5 bits; deflate allows 15");
+static_assert(OP_PNG_CL_MAXBITS >= 5 && OP_PNG_CL_MAXBITS <= 7, "19 codes need 5 bits; a code-length code length is a 3-bit field");
 
 struct op_png {
 	std::vector<unsigned char> bytes;
@@ -257,8 +272,8 @@ __global__ void __launch_bounds__(256) k_png_deflate(const unsigned char* __rest
 		if (!any) S.freq[288] = 1;      // a distance alphabet must describe at least one code
 	}
 	__syncthreads();
-	huff_build(S.freq, 286, 15, S.lens, S.codes, S.hw);
-	huff_build(S.freq + 288, 30, 15, S.lens + 288, S.codes + 288, S.hw);
+	huff_build(S.freq, 286, OP_PNG_LIT_MAXBITS, S.lens, S.codes, S.hw);
+	huff_build(S.freq + 288, 30, OP_PNG_DIST_MAXBITS, S.lens + 288, S.codes + 288, S.hw);
 	if (t == 0) {
 		int hlit = 286, hdist = 30;
 		while (hlit > 257 && !S.lens[hlit - 1]) --hlit;
@@ -286,7 +301,7 @@ __global__ void __launch_bounds__(256) k_png_deflate(const unsigned char* __rest
 		for (int k = 0; k < ncl; ++k) S.clfreq[S.cls[k]]++;
 	}
 	__syncthreads();
-	huff_build(S.clfreq, 19, 7, S.cllens, S.clcodes, S.hw);
+	huff_build(S.clfreq, 19, OP_PNG_CL_MAXBITS, S.cllens, S.clcodes, S.hw);
 	// ---- sizes: this thread's bits, their prefix sum, and the block's form
 	uint32_t mybits = 0;
 	for (int k = 0; k < S.nsym[t]; ++k) {

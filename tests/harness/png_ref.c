@@ -14,7 +14,11 @@
  *             in an EARLIER group of 256 positions of the piece (positions of i's own group are not candidates), if no
  *             farther than 32768.  The longest wins, then the nearest.  A match of length 3 farther than 4096 is dropped.
  *   Huffman   symbols ranked by (count, symbol); Moffat-Katajainen code lengths; Kraft fix-up to the limit (15, 7 for the
- *             code-length alphabet); lengths dealt shortest-first to the highest rank; canonical codes.
+ *             code-length alphabet; the OP_PNG_*_MAXBITS knobs of png.hip); lengths dealt shortest-first to the highest
+ *             rank; canonical codes.
+ *
+ * png_ref_stats reports what the last png_ref_encode went through (which limiter fired, the longest codes, the codes used):
+ * counters only, no byte of the file depends on them.  The tests assert every "this input reaches X" claim from them.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -26,6 +30,35 @@
 #define HASH_BITS 13
 #define TOO_FAR 4096
 #define ADLER_MOD 65521u
+
+/* the same three knobs as png.hip: RFC 1951 bounds code lengths from above only, so a tighter limit still gives a valid file */
+#ifndef OP_PNG_LIT_MAXBITS
+#define OP_PNG_LIT_MAXBITS 15
+#endif
+#ifndef OP_PNG_DIST_MAXBITS
+#define OP_PNG_DIST_MAXBITS 15
+#endif
+#ifndef OP_PNG_CL_MAXBITS
+#define OP_PNG_CL_MAXBITS 7
+#endif
+_Static_assert(OP_PNG_LIT_MAXBITS >= 9 && OP_PNG_LIT_MAXBITS <= 15, "286 codes need 9 bits; deflate allows 15");
+_Static_assert(OP_PNG_DIST_MAXBITS >= 5 && OP_PNG_DIST_MAXBITS <= 15, "30 codes need 5 bits; deflate allows 15");
+_Static_assert(OP_PNG_CL_MAXBITS >= 5 && OP_PNG_CL_MAXBITS <= 7, "19 codes need 5 bits; a code-length code length is a 3-bit field");
+
+/* what the last png_ref_encode went through; index 0 literal / length, 1 distance, 2 code-length alphabet */
+typedef struct {
+	int32_t limited[3];          /* segments in which the Kraft fix-up changed the tree (stored segments included) */
+	int32_t limited_dynamic[3];  /* ... of them written as a dynamic block, i.e. the limited table is in the file */
+	int32_t depth[3];            /* longest code length before the limit */
+	int32_t maxlen[3];           /* longest code length after it */
+	int32_t stored, dynamic;     /* segments of either form */
+	uint32_t len_codes;          /* bit c: length code 257 + c, distance code c, code-length symbol c used in a dynamic segment */
+	uint32_t dist_codes;
+	uint32_t cl_syms;
+	int32_t limited_not_last;    /* a dynamic segment with a limited table that is not the last one */
+	int32_t maxbits[3];          /* the limits this library was compiled with */
+} png_ref_stats_t;
+static png_ref_stats_t g_stats;
 
 static uint32_t crc_table[256];
 static void crc_init(void) {
@@ -93,9 +126,11 @@ static void put_bits(bitw* b, uint32_t v, int n) {
 }
 
 /* ---- Huffman ---- */
-static void huff_build(const uint32_t* freq, int n, int maxbits, unsigned char* lens, uint16_t* codes) {
+/* info (counters only): [0] the fix-up loop ran, [1] longest length before the limit, [2] after it */
+static void huff_build(const uint32_t* freq, int n, int maxbits, unsigned char* lens, uint16_t* codes, int* info) {
 	uint32_t key[288]; int sym[288]; int num[33]; uint32_t next_code[17];
 	int used = 0;
+	info[0] = info[1] = info[2] = 0;
 	memset(lens, 0, (size_t)n);
 	memset(codes, 0, sizeof(uint16_t) * (size_t)n);
 	/* rank by (count, symbol) */
@@ -127,6 +162,7 @@ static void huff_build(const uint32_t* freq, int n, int maxbits, unsigned char* 
 	/* limit the lengths: counts per length, Kraft fix-up */
 	memset(num, 0, sizeof(num));
 	for (int i = 0; i < used; ++i) num[key[i] > 32 ? 32 : key[i]]++;
+	for (int i = 1; i <= 32; ++i) if (num[i]) info[1] = i;
 	if (used > 1) {
 		uint32_t total = 0;
 		for (int i = maxbits + 1; i <= 32; ++i) { num[maxbits] += num[i]; num[i] = 0; }
@@ -135,8 +171,10 @@ static void huff_build(const uint32_t* freq, int n, int maxbits, unsigned char* 
 			num[maxbits]--;
 			for (int i = maxbits - 1; i > 0; --i) if (num[i]) { num[i]--; num[i + 1] += 2; break; }
 			--total;
+			info[0] = 1;
 		}
 	}
+	for (int i = 1; i <= maxbits; ++i) if (num[i]) info[2] = i;
 	/* shortest lengths to the highest ranks */
 	for (int i = 1, j = used; i <= maxbits; ++i) for (int l = num[i]; l > 0; --l) lens[sym[--j]] = (unsigned char)i;
 	/* canonical codes, stored bit-reversed (deflate packs Huffman codes MSB first into an LSB-first stream) */
@@ -227,11 +265,14 @@ static long encode_segment(const unsigned char* F, long N, long s0, long s1, int
 		}
 		nsym[t] = n;
 	}
+	uint32_t dist_used = 0;
+	for (int c = 0; c < 30; ++c) if (freq[288 + c]) dist_used |= 1u << c;      /* before the stand-in code of a match-free segment */
 	freq[256] = 1;
 	{ int any = 0; for (int c = 0; c < 30; ++c) any |= freq[288 + c] != 0; if (!any) freq[288] = 1; }
 	unsigned char lens[320]; uint16_t codes[320];
-	huff_build(freq, 286, 15, lens, codes);
-	huff_build(freq + 288, 30, 15, lens + 288, codes + 288);
+	int info[3][3];
+	huff_build(freq, 286, OP_PNG_LIT_MAXBITS, lens, codes, info[0]);
+	huff_build(freq + 288, 30, OP_PNG_DIST_MAXBITS, lens + 288, codes + 288, info[1]);
 	int hlit = 286, hdist = 30;
 	while (hlit > 257 && !lens[hlit - 1]) --hlit;
 	while (hdist > 1 && !lens[288 + hdist - 1]) --hdist;
@@ -257,7 +298,7 @@ static long encode_segment(const unsigned char* F, long N, long s0, long s1, int
 	uint32_t clfreq[19]; unsigned char cllens[19]; uint16_t clcodes[19];
 	memset(clfreq, 0, sizeof(clfreq));
 	for (int k = 0; k < ncl; ++k) clfreq[cls[k]]++;
-	huff_build(clfreq, 19, 7, cllens, clcodes);
+	huff_build(clfreq, 19, OP_PNG_CL_MAXBITS, cllens, clcodes, info[2]);
 	int hclen = 19;
 	while (hclen > 4 && !cllens[cl_order[hclen - 1]]) --hclen;
 	/* sizes: dynamic block (+ the empty stored block that byte-aligns every segment but the last) against stored blocks */
@@ -275,7 +316,21 @@ static long encode_segment(const unsigned char* F, long N, long s0, long s1, int
 	const long dyn_bytes = last ? (long)((bits + 7) / 8) : (long)((bits + 3 + 7) / 8) + 4;
 	const long nstored = (L + 65534) / 65535;
 	const long stored_bytes = L + 5 * nstored;
-	if (dyn_bytes >= stored_bytes) {
+	const int dynamic = dyn_bytes < stored_bytes;
+	for (int a = 0; a < 3; ++a) {
+		g_stats.limited[a] += info[a][0];
+		if (dynamic) g_stats.limited_dynamic[a] += info[a][0];
+		if (info[a][1] > g_stats.depth[a]) g_stats.depth[a] = info[a][1];
+		if (info[a][2] > g_stats.maxlen[a]) g_stats.maxlen[a] = info[a][2];
+	}
+	if (dynamic) {
+		++g_stats.dynamic;
+		for (int c = 257; c < 286; ++c) if (freq[c]) g_stats.len_codes |= 1u << (c - 257);
+		g_stats.dist_codes |= dist_used;
+		for (int c = 0; c < 19; ++c) if (clfreq[c]) g_stats.cl_syms |= 1u << c;
+		if (!last && (info[0][0] || info[1][0] || info[2][0])) g_stats.limited_not_last = 1;
+	} else ++g_stats.stored;
+	if (!dynamic) {
 		long o = 0;
 		for (long b = 0; b < nstored; ++b) {
 			const long off = b * 65535, n = L - off < 65535 ? L - off : 65535;
@@ -317,11 +372,15 @@ long png_ref_bound(int h, int w) {
 	return 8 + 25 + 14 + 16 + 12 + N + nseg * (12 + 5);
 }
 long png_ref_segment(void) { return SEG; }
+/* the statistics of the last png_ref_encode */
+void png_ref_stats(png_ref_stats_t* out) { *out = g_stats; }
 
 /* H x W x 3 bytes -> the PNG file; returns its size, -1 on bad arguments / too little room */
 long png_ref_encode(const unsigned char* rgb, int h, int w, unsigned char* out, long cap) {
 	if (!rgb || !out || h < 1 || w < 1 || cap < png_ref_bound(h, w)) return -1;
 	crc_init();
+	memset(&g_stats, 0, sizeof(g_stats));
+	g_stats.maxbits[0] = OP_PNG_LIT_MAXBITS; g_stats.maxbits[1] = OP_PNG_DIST_MAXBITS; g_stats.maxbits[2] = OP_PNG_CL_MAXBITS;
 	const long N = (long)h * (1 + 3L * w), nseg = (N + SEG - 1) / SEG;
 	unsigned char* F = (unsigned char*)malloc((size_t)N + 4);
 	unsigned char* slot = (unsigned char*)malloc(SEG + 16);

@@ -364,38 +364,11 @@ def test_raw_extrema_overflow_branches_of_the_row_kernel(oracle, cfg, tmp_path, 
     Both then append straight to the image's list with a global atomic.  A variant of the library compiled with the knobs
     of csrc/pyramid.hip -- an LDS list of FOUR entries / packing refused from 64 px -- runs the same two views in a
     subprocess: descriptors and coordinates equal the oracle's."""
-    import shutil
     import subprocess
     import sys
+    import variant_lib
     root = os.path.dirname(HERE)
-    csrc = os.path.join(root, "openpano_amd", "csrc")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available on this box")
-    base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fopenmp", "-I" + os.path.join(root, "include"), "-I" + csrc]
-    objs = []
-    jobs = []
-    for src in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        stem = os.path.basename(src)[:-4]
-        prebuilt = os.path.join(csrc, stem + ".o")
-        if stem != "pyramid" and os.path.exists(prebuilt):
-            objs.append(prebuilt)
-            continue
-        o = str(tmp_path / (stem + ".o"))
-        jobs.append(subprocess.Popen(base + ([flags] if stem == "pyramid" else []) + ["-c", src, "-o", o]))
-        objs.append(o)
-    for src in sorted(glob.glob(os.path.join(csrc, "*.cc"))):           # host-only translation units of the library (plain g++, csrc/Makefile)
-        stem = os.path.basename(src)[:-3]
-        prebuilt = os.path.join(csrc, stem + ".o")
-        if os.path.exists(prebuilt):
-            objs.append(prebuilt)
-            continue
-        o = str(tmp_path / (stem + ".o"))
-        jobs.append(subprocess.Popen(["g++", "-std=c++17", "-O3", "-ffp-contract=off", "-fPIC", "-Wno-psabi", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + csrc, "-c", src, "-o", o]))
-        objs.append(o)
-    assert all(j.wait() == 0 for j in jobs)
-    lib = str(tmp_path / "libopenpano_hip_variant.so")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fopenmp", "-o", lib] + objs)
+    lib = variant_lib.build_variant(tmp_path, "pyramid", [flags])
     views = [_view(400, 600, 1), _view(300, 500, 5)]
     np.savez(tmp_path / "in.npz", a=views[0], b=views[1])
     code = ("import sys, numpy as np; sys.path.insert(0, %r)\n"

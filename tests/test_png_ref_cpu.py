@@ -5,9 +5,17 @@
    binascii.crc32 and zlib.decompressobj, nothing else -- accepts and un-filters to exactly the input, for every input of
    png_cases.CASES; PIL, where present, reads the same pixels;
 3. sizes: never above the stored form plus framing; the all-background canvas of config 4 at least 100-fold;
-4. the deflate stage against zlib level 1 on the same filtered bytes, on photographic content (measured bounds)."""
+4. the deflate stage against zlib level 1 on the same filtered bytes, on photographic content (measured bounds);
+5. png_ref_stats: every crafted input of png_cases.REACHES reaches the limiter it was built for, at the shipped limits;
+6. the restatement compiled with the limits 11 / 11 / 5 (the knobs it shares with png.hip) still writes files the decoder
+   accepts, no code is longer than its limit, and over the inputs the limiter of every alphabet fires;
+7. at the shipped limits the restatement writes the files recorded in tests/golden/png_ref_digests.json -- taken before the
+   knobs and the statistics existed: neither changed a byte."""
 import ctypes as C
+import hashlib
 import io
+import json
+import os
 import zlib
 
 import numpy as np
@@ -22,9 +30,32 @@ from openpano_amd import hip
 RATIO_BOUND = {"natural_400x600": 1.10, "blended": 1.00}
 
 
+# all255_763x7999 (299 segments, 18 MB) is left to the shipped limits: no tree in it is deeper than 4
+VARIANT_CASES = [n for n in png_cases.CASES if n != "all255_763x7999"]
+DIGESTS = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "png_ref_digests.json")))
+
+
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
     return png_cases.build_ref(tmp_path_factory.mktemp("pngref"))
+
+
+@pytest.fixture(scope="module")
+def variant(tmp_path_factory):
+    return png_cases.build_ref(tmp_path_factory.mktemp("pngref_variant"), png_cases.VARIANT_FLAGS)
+
+
+@pytest.fixture(scope="module")
+def variant_runs(variant):
+    """name -> (input, file, statistics) of the variant restatement, every input encoded once"""
+    runs = {}
+    for name in VARIANT_CASES:
+        if name in png_cases.NEEDS_PIL and not png_cases.natural.available():
+            continue
+        rgb = png_cases.case(name)
+        png = png_cases.ref_encode(variant, rgb)
+        runs[name] = (rgb, png, png_cases.ref_stats(variant))
+    return runs
 
 
 def test_abi_12_and_symbols():
@@ -85,3 +116,75 @@ def test_deflate_stage_against_zlib_level_1(ref, name):
     print(f"{name}: IDAT payload {ours}, zlib level 1 {theirs}, ratio {ratio:.4f}")
     assert RATIO_BOUND[name] <= 1.30
     assert ratio <= RATIO_BOUND[name], ratio
+
+
+@pytest.mark.parametrize("name", list(png_cases.REACHES))
+def test_crafted_input_reaches_its_limiter(ref, name):
+    """The shipped limits (15 / 15 / 7) are out of reach of ordinary images; these inputs are in the suite only because the
+    Kraft fix-up of huff_build rewrites their tree, which png_ref_stats has to confirm -- in a dynamic segment, so that the
+    rewritten table is in the file, and for one input in a segment that is not the last."""
+    want = png_cases.REACHES[name]
+    rgb = png_cases.case(name)
+    png_cases.ref_encode(ref, rgb)
+    s = png_cases.ref_stats(ref)
+    print(name, s)
+    a = want["alphabet"]
+    assert tuple(s.maxbits) == png_cases.MAXBITS
+    assert s.limited_dynamic[a] == want["segments"] and s.depth[a] == want["depth"] > png_cases.MAXBITS[a]
+    assert s.maxlen[a] == png_cases.MAXBITS[a]
+    assert bool(s.limited_not_last) == want["not_last"]
+    h, w, _ = rgb.shape
+    assert s.stored + s.dynamic == -(-(h * (1 + 3 * w)) // png_cases.SEG)
+
+
+def test_statistics_of_the_ordinary_inputs(ref):
+    """what the statistics say where the answer is known: incompressible input is stored, the shipped limits are not reached by
+    the smooth inputs, and length code 285 (a match of 258) never occurs because a match ends with its 240-byte sub-block"""
+    png_cases.ref_encode(ref, png_cases.case("random_97x211"))
+    s = png_cases.ref_stats(ref)
+    assert (s.stored, s.dynamic, s.len_codes, s.dist_codes, s.cl_syms) == (2, 0, 0, 0, 0)
+    png_cases.ref_encode(ref, png_cases.case("two_segments_120x341"))
+    s = png_cases.ref_stats(ref)
+    assert (s.stored, s.dynamic) == (0, 2) and list(s.limited) == [0, 0, 0] and not s.limited_not_last
+    assert list(s.depth) == list(s.maxlen) and s.maxlen[png_cases.DIST] == 15
+    assert s.dist_codes == (1 << 30) - 1                       # every distance code
+    png_cases.ref_encode(ref, png_cases.case("checker_200x300"))
+    s = png_cases.ref_stats(ref)
+    assert s.len_codes == (1 << 28) - 1                        # length codes 257..284: all but 285
+
+
+@pytest.mark.parametrize("name", VARIANT_CASES)
+def test_variant_limits_still_decode(variant_runs, name):
+    if name not in variant_runs:
+        pytest.skip("PIL not available")
+    rgb, png, s = variant_runs[name]
+    h, w, _ = rgb.shape
+    print(name, s)
+    assert tuple(s.maxbits) == png_cases.VARIANT_MAXBITS
+    assert all(s.maxlen[a] <= png_cases.VARIANT_MAXBITS[a] for a in range(3))
+    assert all((s.depth[a] > png_cases.VARIANT_MAXBITS[a]) == (s.limited[a] > 0) for a in range(3))
+    d = png_cases.decode(png)
+    assert (d["h"], d["w"]) == (h, w) and np.array_equal(d["pixels"], rgb)
+    assert len(png) <= png_cases.stored_bound(h, w)
+
+
+def test_variant_limits_fire_in_every_alphabet(variant_runs):
+    """over the inputs (with or without the natural crop), 11 / 11 / 5 makes the limiter of each alphabet rewrite a table that
+    is written to the file, and in a segment that is not the last"""
+    for a in range(3):
+        assert sum(s.limited_dynamic[a] for _, _, s in variant_runs.values()) > 0, a
+    assert any(s.limited_not_last for _, _, s in variant_runs.values())
+
+
+@pytest.mark.parametrize("name", list(DIGESTS))
+def test_shipped_limits_write_the_recorded_files(ref, name):
+    rgb = png_cases.case(name)
+    want = DIGESTS[name]
+    if "input_sha256" in want and hashlib.sha256(rgb.tobytes()).hexdigest() != want["input_sha256"]:
+        pytest.skip("this JPEG decoder gives other pixels than the one the digest was recorded with")
+    png = png_cases.ref_encode(ref, rgb)
+    assert (len(png), hashlib.sha256(png).hexdigest()) == (want["bytes"], want["sha256"])
+
+
+def test_digests_cover_the_inputs_that_predate_them():
+    assert list(DIGESTS) == list(png_cases.CASES)[:13] and set(png_cases.REACHES) == set(list(png_cases.CASES)[13:])
