@@ -55,6 +55,10 @@ int orc_match_exact(const orc_sift_cfg* cfg, const float* d1, int n1, const floa
 			else if (dist < next_min) next_min = dist;
 		}
 		if (min > REJECT_RATIO_SQR * next_min) continue;
+		/* No distance was finite (a NaN descriptor): under a ratio below 1 the test above has already refused the row
+		 * (FLT_MAX > r^2 FLT_MAX); from 1.0 on it has not, and the reference goes on to feat2[-1] (matcher.cc:54), which is
+		 * undefined.  Such a row never matches here, at any ratio -- what the device does (finish_forward, match.hip). */
+		if (min_idx < 0) continue;
 		const float* dsc2 = pf2 + 128 * (size_t)min_idx;
 		for (int kk = 0; kk < l1; ++kk) if (kk != k) {
 			float dist = orc_euclidean_sqr(dsc2, pf1 + 128 * (size_t)kk, 128, next_min);

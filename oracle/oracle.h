@@ -88,6 +88,22 @@ int orc_ransac(const int* match, int m, const double* kp1, int nk1, const double
 		float inlier_in_match_ratio, float inlier_in_points_ratio, unsigned seed,
 		float* confidence, double* homo_out, int* inliers, int* n_inliers, int* best_hyp, int* best_count);
 
+/* where this thread's last orc_ransac call left get_transform / fill_inliers_to_matchinfo (:55, :85, :154-216) */
+enum {
+	ORC_RANSAC_EXIT_DEAD = 0,		/* m < 8 or m < the sample size */
+	ORC_RANSAC_EXIT_NO_HEALTHY,		/* no hypothesis passed Homography::health */
+	ORC_RANSAC_EXIT_FEW_INLIERS,		/* fewer than 8 inliers */
+	ORC_RANSAC_EXIT_SINGULAR,		/* the refit has no inverse */
+	ORC_RANSAC_EXIT_MATCH_RATIO_1,		/* first image: inliers / matches in the overlap < INLIER_IN_MATCH_RATIO */
+	ORC_RANSAC_EXIT_POINT_RATIO_1,		/* first image: inliers / keypoints in the overlap outside [0.01, 1], or no polygon */
+	ORC_RANSAC_EXIT_MATCH_RATIO_2,		/* second image's match-ratio gate */
+	ORC_RANSAC_EXIT_POINT_RATIO_2,		/* second image's keypoint-ratio gate */
+	ORC_RANSAC_EXIT_CONFIDENCE,		/* confidence < INLIER_IN_POINTS_RATIO */
+	ORC_RANSAC_EXIT_AREA,			/* overlap area / larger image area < 0.15 */
+	ORC_RANSAC_EXIT_ACCEPTED
+};
+int orc_ransac_last_exit(void);
+
 /* ---- warp + blend: ConnectedImages::blend (stitch/stitcher_image.cc:116-155) with
  * LinearBlender (stitch/blender.cc:24-96) or MultiBandBlender (stitch/multiband.cc:19-151) ---- */
 typedef struct {

@@ -272,6 +272,10 @@ static int count_in(const p2* poly, int n, const p2* pts, int npts, int* valid) 
 	return c;
 }
 
+/* where the last orc_ransac call of this thread left (ORC_RANSAC_EXIT_*, oracle.h) */
+static __thread int last_exit = ORC_RANSAC_EXIT_DEAD;
+int orc_ransac_last_exit(void) { return last_exit; }
+
 /* TransformEstimation(match, kp1, kp2, shape1, shape2).get_transform(info) with an injected seed.
  * match: m x (first, second); kp1/kp2: centred keypoints (x, y); affine = CYLINDER || TRANS.
  * Outputs: *confidence, homo[9], inliers (<= m ints) + *n_inliers, *best_hyp/*best_count.
@@ -282,6 +286,7 @@ int orc_ransac(const int* match, int m, const double* kp1, int nk1, const double
 		float* confidence, double* homo_out, int* inliers, int* n_inliers, int* best_hyp, int* best_count) {
 	*confidence = 0; *n_inliers = 0; *best_hyp = -1; *best_count = -1;
 	const int nused = (affine ? 6 : 8) / 2 + 4;
+	last_exit = ORC_RANSAC_EXIT_DEAD;
 	if (m < nused || m < 8) return 0;	/* :55 and ESTIMATE_MIN_NR_MATCH (:21,39) */
 	p2* q1 = (p2*)malloc(sizeof(p2) * m); p2* q2 = (p2*)malloc(sizeof(p2) * m);
 	for (int i = 0; i < m; ++i) {
@@ -312,17 +317,20 @@ int orc_ransac(const int* match, int m, const double* kp1, int nk1, const double
 	}
 	*best_count = maxcnt;
 	int ok = 0;
+	last_exit = ORC_RANSAC_EXIT_NO_HEALTHY;
 	if (have) {
 		int ni = 0;
 		for (int i = 0; i < m; ++i) if (is_inlier(best, q1[i], q2[i], inlier_dist)) inliers[ni++] = i;
 		*n_inliers = ni;
 		*confidence = -(float)ni;	/* :153 */
+		last_exit = ORC_RANSAC_EXIT_FEW_INLIERS;
 		if (ni >= 8) {
 			p2* a1 = (p2*)malloc(sizeof(p2) * ni); p2* a2 = (p2*)malloc(sizeof(p2) * ni);
 			for (int i = 0; i < ni; ++i) { a1[i] = q1[inliers[i]]; a2[i] = q2[inliers[i]]; }
 			double homo[9], inv[9];
 			calc_transform(ni, a1, a2, affine, homo);
 			free(a1); free(a2);
+			last_exit = ORC_RANSAC_EXIT_SINGULAR;
 			if (inverse3(homo, inv)) {
 				p2 hull[420]; int valid;
 				p2* k1 = (p2*)malloc(sizeof(p2) * (nk1 > 0 ? nk1 : 1)); p2* k2 = (p2*)malloc(sizeof(p2) * (nk2 > 0 ? nk2 : 1));
@@ -331,20 +339,27 @@ int orc_ransac(const int* match, int m, const double* kp1, int nk1, const double
 				do {
 					int nh = overlap_region(w1, h1, w2, h2, homo, inv, hull);
 					float r1m = ni * 1.0f / count_in(hull, nh, q1, m, &valid);
+					last_exit = ORC_RANSAC_EXIT_MATCH_RATIO_1;
 					if (r1m < inlier_in_match_ratio) break;
 					float r1p = ni * 1.0f / count_in(hull, nh, k1, nk1, &valid);
+					last_exit = ORC_RANSAC_EXIT_POINT_RATIO_1;
 					if (!valid || r1p < 0.01 || r1p > 1) break;
 					nh = overlap_region(w2, h2, w1, h1, inv, homo, hull);
 					float r2m = ni * 1.0f / count_in(hull, nh, q2, m, &valid);
+					last_exit = ORC_RANSAC_EXIT_MATCH_RATIO_2;
 					if (r2m < inlier_in_match_ratio) break;
 					float r2p = ni * 1.0f / count_in(hull, nh, k2, nk2, &valid);
+					last_exit = ORC_RANSAC_EXIT_POINT_RATIO_2;
 					if (!valid || r2p < 0.01 || r2p > 1) break;
 					*confidence = (float)((r1p + r2p) * 0.5);
+					last_exit = ORC_RANSAC_EXIT_CONFIDENCE;
 					if (*confidence < inlier_in_points_ratio) break;
 					double area = polygon_area(hull, nh);
 					double area1 = (double)(w1 * h1), area2 = (double)(w2 * h2);
+					last_exit = ORC_RANSAC_EXIT_AREA;
 					if (area / (area1 > area2 ? area1 : area2) < 0.15) break;
 					memcpy(homo_out, homo, sizeof(homo));
+					last_exit = ORC_RANSAC_EXIT_ACCEPTED;
 					ok = 1;
 				} while (0);
 				free(k1); free(k2);

@@ -137,6 +137,9 @@ class _StagedBase:
 
 
 GAIN_NONE, GAIN_IMAGE, GAIN_BLOCK, GAIN_VIGNETTE = 0, 1, 2, 3      # oracle.h: ORC_GAIN_*
+# oracle.h: ORC_RANSAC_EXIT_*, in the enum's order (what orc_ransac_last_exit returns)
+RANSAC_EXITS = ("DEAD", "NO_HEALTHY", "FEW_INLIERS", "SINGULAR", "MATCH_RATIO_1", "POINT_RATIO_1", "MATCH_RATIO_2",
+                "POINT_RATIO_2", "CONFIDENCE", "AREA", "ACCEPTED")
 
 
 def gain_table(n, gains=None, vignette=None):
@@ -186,6 +189,8 @@ class Oracle(_StagedBase):
         lib.orc_ransac.argtypes = [_i32p, C.c_int, _f64p, C.c_int, _f64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_uint,
                                    C.POINTER(C.c_float), _f64p, _i32p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.orc_ransac_last_exit.restype = C.c_int
+        lib.orc_ransac_last_exit.argtypes = []
 
         lib.orc_match_pairs_batch.restype = C.c_long
         lib.orc_match_pairs_batch.argtypes = [C.c_void_p, _f32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int]
@@ -279,7 +284,8 @@ class Oracle(_StagedBase):
 
     def ransac(self, match, kp1, kp2, shape1, shape2, seed, cfg=None):
         """TransformEstimation(...).get_transform with an injected mt19937 seed.
-        shape = (w, h). -> dict(ok, confidence, homo, inliers (match indices), best_hyp, best_count)"""
+        shape = (w, h). -> dict(ok, confidence, homo, inliers (match indices), best_hyp, best_count, exit: the name in
+        RANSAC_EXITS of where the call left)"""
         cfg = cfg or self.cfg
         match = np.ascontiguousarray(match, np.int32).reshape(-1, 2)
         kp1 = np.ascontiguousarray(kp1, np.float64).reshape(-1, 2); kp2 = np.ascontiguousarray(kp2, np.float64).reshape(-1, 2)
@@ -293,7 +299,7 @@ class Oracle(_StagedBase):
                                  cfg.RANSAC_INLIER_THRES, cfg.INLIER_IN_MATCH_RATIO, cfg.INLIER_IN_POINTS_RATIO, int(seed),
                                  C.byref(conf), homo, inl, C.byref(ni), C.byref(bh), C.byref(bc))
         return dict(ok=bool(ok), confidence=conf.value, homo=homo.reshape(3, 3), inliers=inl[: ni.value].copy(),
-                    best_hyp=bh.value, best_count=bc.value)
+                    best_hyp=bh.value, best_count=bc.value, exit=RANSAC_EXITS[self.lib.orc_ransac_last_exit()])
 
     def sift_stages(self, img, planes=True):
         img = np.ascontiguousarray(img, np.float32)

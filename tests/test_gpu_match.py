@@ -48,8 +48,8 @@ def test_all_pairs_on_sift_features(ctx, oracle, cfg):
     f.free()
 
 
-def test_edge_cases(ctx, oracle, cfg):
-    from openpano_amd import hip
+def _edge_sets():
+    """the descriptor sets of test_edge_cases (also matched under other ratios: test_gpu_match_ransac_config.py)"""
     rng = np.random.default_rng(1)
     a = np.load(os.path.join(HERE, "golden", "sift_a_240x320.npz"))["desc"]
     sets = [
@@ -69,6 +69,12 @@ def test_edge_cases(ctx, oracle, cfg):
         # 11: a NaN descriptor (zero-weight window) never matches and never wins a ratio test
         np.concatenate([a[:30], np.full((1, 128), np.nan, np.float32), a[30:50]]),
     ]
+    return sets
+
+
+def test_edge_cases(ctx, oracle, cfg):
+    from openpano_amd import hip
+    sets = _edge_sets()
     f = hip.Features.from_host(ctx, sets)
     pairs = [(i, j) for i in range(len(sets)) for j in range(len(sets)) if i != j]
     got = hip.match_pairs(ctx, cfg, f, pairs)
@@ -81,13 +87,8 @@ def test_edge_cases(ctx, oracle, cfg):
     f.free()
 
 
-def test_near_ties_across_tiles_and_lane_halves(ctx, oracle, cfg):
-    """The sweep keeps a top-4 of KEYS per lane half (column & 4 of every 32-column tile selects the half) and
-    re-scores every kept entry within the error margin of the row's 2nd best.  Near-copies of a row (inside the
-    margin: |delta d^2| of a few units on |x|^2 = 512^2) are planted at chosen columns -- same tile / different
-    tiles, same half / both halves, 2 to 6 copies (up to 3 + 3 candidates; 4 in one half = exact full scan) --
-    and the match sets must equal the exact matcher's, forward and reverse."""
-    from openpano_amd import hip
+def _near_tie_sets():
+    """x, y of test_near_ties_across_tiles_and_lane_halves: near-copies of x's rows planted at chosen columns of y"""
     rng = np.random.default_rng(77)
     a = np.load(os.path.join(HERE, "golden", "sift_d_500x700.npz"))["desc"]
     x = a[:96].copy()
@@ -110,6 +111,17 @@ def test_near_ties_across_tiles_and_lane_halves(ctx, oracle, cfg):
             if k > 0 or r % 2:       # exact duplicate for even rows' first copy, otherwise a near-copy
                 j = rng.integers(0, 128, 3)
                 y[c, j] = np.maximum(y[c, j] + rng.choice([-0.25, 0.25, 0.5], 3).astype(np.float32), 0)
+    return x, y
+
+
+def test_near_ties_across_tiles_and_lane_halves(ctx, oracle, cfg):
+    """The sweep keeps a top-4 of KEYS per lane half (column & 4 of every 32-column tile selects the half) and
+    re-scores every kept entry within the error margin of the row's 2nd best.  Near-copies of a row (inside the
+    margin: |delta d^2| of a few units on |x|^2 = 512^2) are planted at chosen columns -- same tile / different
+    tiles, same half / both halves, 2 to 6 copies (up to 3 + 3 candidates; 4 in one half = exact full scan) --
+    and the match sets must equal the exact matcher's, forward and reverse."""
+    from openpano_amd import hip
+    x, y = _near_tie_sets()
     f = hip.Features.from_host(ctx, [x, y, y[:40], x[:5]])
     pairs = [(0, 1), (1, 0), (2, 0), (0, 2), (3, 1), (1, 3)]
     sets = [x, y, y[:40], x[:5]]

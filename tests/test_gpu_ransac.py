@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from openpano_amd import synth
+from ransac_scenes import check as _check
 
 pytestmark = pytest.mark.gpu
 
@@ -15,17 +16,6 @@ def ctx():
     c = hip.Context(0)
     yield c
     c.close()
-
-
-def _check(oracle, got, m, ca, cb, s1, s2, seed, cfg=None):
-    want = oracle.ransac(m, ca, cb, s1, s2, seed, cfg=cfg)
-    assert got["best_hyp"] == want["best_hyp"] and got["best_count"] == want["best_count"]
-    assert got["ok"] == want["ok"]
-    assert got["confidence"] == want["confidence"]
-    assert np.array_equal(got["inliers"], want["inliers"])
-    if want["ok"]:
-        assert np.array_equal(got["homo"], want["homo"])
-    return want
 
 
 def test_all_pairs_ransac_vs_oracle(ctx, oracle, cfg):

@@ -49,3 +49,38 @@ def test_key_error_stays_inside_the_budget():
                 worst = max(worst, float(np.max(np.abs(key - true) / scale)))
     assert worst <= 3.3e-5, worst
     assert worst > 1e-7                                  # the model really rounds
+
+
+def _key_matrix(x, y):
+    """_keys for every row of x against every row of y"""
+    xh = _bf16(x); xl = _bf16(x - xh)
+    yh = _bf16(y); yl = _bf16(y - yh)
+    ny = np.zeros(len(y), np.float32)
+    for k in range(128):
+        ny = (ny + y[:, k] * y[:, k]).astype(np.float32)
+    acc = np.repeat((-(ny * np.float32(0.5))).astype(np.float32)[None], len(x), 0)
+    for k in range(128):
+        for a, b in ((xh, yh), (xh, yl), (xl, yh)):
+            acc = (acc + (a[:, k, None] * b[None, :, k]).astype(np.float32)).astype(np.float32)
+    return (acc.view(np.uint32) & np.uint32(0xFFFFFFF0)).view(np.float32)
+
+
+def test_a_margin_from_the_rows_own_norm_loses_candidates():
+    """E uses the largest norm of the CALL, not the row's: the key error goes with |y|^2.  On the small-norm rows against
+    large-norm columns that tests/test_gpu_match_ransac_config.py::test_one_call_mixing_magnitudes matches on the device,
+    the shipped margin keeps the exact best and second best of every row among the candidates (keys within E of the
+    second-largest key); 8.2e-5 * 2 |x|^2 drops one of them for several rows -- so that test can tell the two apart."""
+    from test_gpu_match_ransac_config import MARGIN, _tight_ties
+    x, y = _tight_ties()
+    key = _key_matrix(x, y).astype(np.float64)
+    x64, y64 = x.astype(np.float64), y.astype(np.float64)
+    dist = (x64 ** 2).sum(1)[:, None] + (y64 ** 2).sum(1)[None] - 2 * x64 @ y64.T
+    nx, gmax = (x64 ** 2).sum(1), float((y64 ** 2).sum(1).max())
+    lost = {}
+    for name, E in (("call", MARGIN * (nx + gmax)), ("row", MARGIN * 2 * nx)):
+        n = 0
+        for r in range(len(x)):
+            kept = key[r] >= np.sort(key[r])[-2] - E[r]
+            n += not kept[np.argsort(dist[r], kind="stable")[:2]].all()
+        lost[name] = n
+    assert lost["call"] == 0 and lost["row"] >= 5, lost
