@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from openpano_amd import synth
+from sift_cases import _compare_stages
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,25 +47,6 @@ def test_device_math_equals_libm(ctx, oracle):
     x[:5] = [0, 0, 1e-7, -3e-7, 0.5]; y[:5] = [0, 1e-7, 0, 2e-7, -0.5]
     assert np.array_equal(hip.debug_math(ctx, 3, x, y), oracle.libm(3, x, y))
     assert np.array_equal(hip.debug_math(ctx, 4, x, y), oracle.libm(4, x, y))
-
-
-def _compare_stages(g, o, cfg):
-    assert g.dims == o.dims
-    assert np.array_equal(g.work, o.work), "working image"
-    for oc in range(cfg.NUM_OCTAVE):
-        assert np.array_equal(g.grey[oc], o.gauss[(oc, 0)]), ("grey", oc)
-    for kind in ("dog", "mag", "ort"):
-        a, b = getattr(g, kind), getattr(o, kind)
-        for k in a:
-            assert np.array_equal(a[k], b[k]), (kind, k, int((a[k] != b[k]).sum()))
-    for k in g.raw:
-        assert np.array_equal(g.raw[k], o.raw[k]), ("raw", k)
-    for nm in ("refined", "oriented"):
-        a, b = getattr(g, nm), getattr(o, nm)
-        for f in ("ints", "real", "fl"):
-            assert np.array_equal(a[f], b[f]), (nm, f)
-    assert np.array_equal(g.desc, o.desc), int((g.desc != o.desc).sum())
-    assert np.array_equal(g.coor, o.coor)
 
 
 VIEWS = [("cfg2_600x400", 400, 600, 22), ("cfg4_1300x867", 867, 1300, 38), ("odd_333x777", 333, 777, 5),
