@@ -13,7 +13,8 @@
  *     message of the calling thread's last failure (the adapters turn it into the reference's
  *     error_exit(), lib/debugutils.cc:57-60); no exception crosses the ABI;
  *   - images are the reference's Mat32f layout (lib/mat.h:8-57): row-major H x W x 3 fp32 in
- *     [0,1]; a pointer may be host or device memory (flag on_device);
+ *     [0,1], or the decoder's bytes in the same layout (OP_U8 / OP_SRC_U8), read as (float)byte / 255.0 like read_img
+ *     does; a pointer may be host or device memory (flag on_device);
  *   - there is NO CPU fallback: without a gfx950 device every compute entry point fails.
  */
 #ifndef OPENPANO_HIP_H
@@ -304,9 +305,17 @@ int op_pairwise_table(op_ctx* ctx, const op_features* f, const op_matches* m, co
  * Multiband: a cfg->MULTIBAND / cfg->GAUSS_WINDOW_FACTOR whose blur at some level is wider than 31 taps (GaussCache's
  * half-width above 15: wf at levels 0-2, 1.5 wf at 3-8, 2 wf at 9) returns OP_ERR_UNSUPPORTED, before any device work.
  * ===================================================================================== */
+enum { OP_SRC_DEVICE = 1, OP_SRC_U8 = 2 };   /* bits of op_blend_image.on_device */
 typedef struct op_blend_image {
-	const float* data;    /* H x W x 3 fp32 (ImageRef::img, stitch/imageref.hh:15-17) */
+	const float* data;    /* H x W x 3 fp32 (ImageRef::img, stitch/imageref.hh:15-17); with OP_SRC_U8: H x W x 3 bytes behind the same pointer */
 	int h, w;
+	/* A flag word.  Bit 0, OP_SRC_DEVICE: data is a device pointer (0 and 1 mean what they always meant).  Bit 1, OP_SRC_U8:
+	 * data points at mat_h x mat_w x 3 decoder bytes; a sample's four taps are converted on the device exactly like read_img
+	 * does, (float)byte / 255.0 (lib/imgio.cc:55-57,78-80), then interpolated in the reference's fp32 sequence: the canvas
+	 * and the overlap statistics equal, bit for bit, those of the fp32 view that conversion produces.  A byte view holds no
+	 * Color::NO.  A host byte view uploads 3 h w bytes instead of 12 h w; a device byte view may lie at any alignment and
+	 * only its own bytes are read.  Sets may mix both types.  Any other bit: OP_ERR_INVALID, before any device work.
+	 * Accepted by op_blend, op_blend_gains, op_blend_block_gains, op_blend_vignette and the three overlap passes. */
 	int on_device;
 	double homo_inv[9];   /* ImageComponent::homo_inv (stitch/stitcher_image.hh:40-42) */
 	double range[4];      /* ImageComponent::range: min.x, min.y, max.x, max.y (:48) */
@@ -485,10 +494,31 @@ void op_png_free(op_png* p);
 
 /* CYLINDER mode pre-warp -- replaces CylinderWarper::warp (stitch/warp.hh:47-55, warp.cc:13-75).
  * op_cyl_warp_shape is the host part (projector, output shape, offset and the keypoints, which
- * are centred coordinates updated in place: warp.cc:46-67); op_cyl_warp renders the pixels. */
+ * are centred coordinates updated in place: warp.cc:46-67); op_cyl_warp renders the pixels.  The image may be OP_F32 or
+ * OP_U8 (bytes converted in the sampler as for OP_SRC_U8); the result is the same fp32 canvas either way. */
 int op_cyl_warp_shape(const op_config* cfg, int w, int h, double h_factor, double* pts, int npts,
 		int* new_w, int* new_h, double* offset);
 int op_cyl_warp(op_ctx* ctx, const op_config* cfg, const op_image* img, double h_factor, op_canvas** out);
+
+/* ---- RESIDENT VIEWS -- the seam of ImageRef::load / ImageRef::img (stitch/imageref.hh:15-31): the reference loads every
+ * view once and every stage reads that Mat.  An op_views holds the views of a job in library-owned device memory, each in
+ * the type it arrived in (OP_F32 or OP_U8), so that SIFT, the cylinder warp, the overlap passes and every blend read ONE
+ * upload: decoder bytes are a quarter of the PCIe and HBM traffic of their fp32 form and give the same results bit for bit.
+ * op_views_upload: copies n host or device images (op_image; on_device 0 or 1); host images of one size at one constant
+ * stride go up in one copy, as in op_sift_batch.  The sources are free again when it returns.
+ * op_views_image: view i as a device op_image, for op_sift_batch / op_cyl_warp.
+ * op_views_blend_image: fills data, h, w, the flag word and mat_h = mat_w = 0 of *out; homo_inv and range are left alone.
+ * op_views_count: the number of views.  Bad arguments (NULLs, n < 1, an index out of range, sizes below 2, an unknown
+ * dtype) return OP_ERR_INVALID, before any device work.
+ * op_views_free: waits for the stream of the context the views were uploaded with, then releases the memory; every
+ * op_image / op_blend_image taken from the object dangles afterwards.  An op_views must not outlive its context.
+ * Threading as the rest: one call at a time per context. */
+typedef struct op_views op_views;
+int op_views_upload(op_ctx* ctx, const op_image* imgs, int n, op_views** out);
+int op_views_count(const op_views* v);
+int op_views_image(const op_views* v, int i, op_image* out);
+int op_views_blend_image(const op_views* v, int i, op_blend_image* out);
+void op_views_free(op_views* v);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,12 @@
 #include <cmath>
 #include <cstring>
 
+struct op_views {
+	op_ctx* ctx = nullptr;
+	char* block = nullptr;            // one pool block; view i at imgs[i].data, a multiple of 256 bytes into it
+	std::vector<op_image> imgs;       // device images, each in its own dtype
+};
+
 struct op_canvas {
 	float* data = nullptr;   // device, h x w x 3
 	int h = 0, w = 0;
@@ -41,12 +47,13 @@ struct op_canvas {
 namespace {
 
 struct BlendImg {
-	const float* data; int h, w;   // ImageRef::height()/width(): bounds, weights, centre
+	const void* data; int h, w;    // ImageRef::height()/width(): bounds, weights, centre.  data: fp32, or bytes when u8 is set
 	int mh, mw;                    // rows / cols of the pixel buffer (differ after a cylinder pre-warp, see op_blend_image)
 	int x0, y0, x1, y1;        // ROI on the canvas, inclusive (BlenderBase::Range, blender.hh:19-27)
 	double hinv[9];
 	long long roi_off;         // multiband: offset (pixels) of this image's ROI planes
 	int rw, rh;
+	int u8;                    // OP_SRC_U8: data holds mh x mw x 3 decoder bytes (read only by the U8 instances of the kernels)
 };
 
 struct BlendGeom { int method; double minx, miny, resx, resy; };
@@ -75,10 +82,19 @@ __device__ __forceinline__ void space_to_image(const BlendImg& im, double hx, do
 	oy = ry * denom + im.h * 0.5;
 }
 
+// interpolate()'s bounds, fr < 0 || fc < 0 || fc + 1 >= cols || fr + 1 >= rows with fr = floor(r), fc = floor(c), tested on the
+// floats: the same answer for every coordinate an int holds, and "outside" for the rest.  The multiband first level passes
+// coordinates it has not bounded: a canvas pixel 90 degrees off a view's axis (any panorama wider than half a turn has them
+// inside the ROI of a view that straddles the seam) maps to |coordinate| > 2^31, whose conversion saturates, fr + 1 wraps
+// and the int test lets the taps through -- a read far outside the image.
+__device__ __forceinline__ bool in_taps(int rows, int cols, float r, float c) {
+	return r >= 0.f && c >= 0.f && r < (float)(rows - 1) && c < (float)(cols - 1);
+}
+
 // interpolate (lib/imgproc.cc:135-156); false = Color::NO
 __device__ __forceinline__ bool interpolate(const float* __restrict__ img, int rows, int cols, float r, float c, float (&out)[3]) {
+	if (!in_taps(rows, cols, r, c)) return false;
 	const int fr = (int)floorf(r), fc = (int)floorf(c);
-	if (fr < 0 || fc < 0 || fc + 1 >= cols || fr + 1 >= rows) return false;
 	r -= (float)fr; c -= (float)fc;
 	const float* p00 = img + ((long long)fr * cols + fc) * 3;
 	const float* p10 = p00 + (long long)cols * 3;
@@ -100,6 +116,53 @@ __device__ __forceinline__ bool interpolate(const float* __restrict__ img, int r
 	r0 += d0 * w; r1 += d1 * w; r2 += d2 * w;
 	out[0] = r0; out[1] = r1; out[2] = r2;
 	return true;
+}
+
+// A decoder byte as a source pixel: read_img's (float)((double)b / 255.0) (lib/imgio.cc:55-57,78-80).  Evaluated as
+// (float)((double)b * (1.0 / 255.0)) -- three instructions, no table to set up, and equal to the division for all 256
+// bytes (tests/test_views_cpu.py); (float)b * (1.f / 255.f) is not (126 of 256 differ).
+__device__ __forceinline__ float byte_pixel(unsigned b) { return (float)((double)b * (1.0 / 255.0)); }
+
+// interpolate() for an image of decoder bytes (OP_SRC_U8): the four taps are converted as read_img would have, then the
+// fp32 sequence above, unchanged.  A byte image holds no Color::NO, so the four `< 0` tests fall away.  The footprint is two
+// runs of 6 bytes at byte offset 3 (fr cols + fc) -- any alignment mod 4 -- read with byte loads: nothing outside
+// [img, img + 3 rows cols) is touched, whatever the alignment of a caller-owned pointer.  (Aligned dword loads +
+// v_alignbyte with the image's first and last dwords guarded measured 8 % slower: DESIGN section 12.)
+__device__ __forceinline__ bool interpolate_u8(const unsigned char* __restrict__ img, int rows, int cols, float r, float c, float (&out)[3]) {
+	if (!in_taps(rows, cols, r, c)) return false;
+	const int fr = (int)floorf(r), fc = (int)floorf(c);
+	r -= (float)fr; c -= (float)fc;
+	const unsigned char* p00 = img + ((long long)fr * cols + fc) * 3;
+	const unsigned char* p10 = p00 + (long long)cols * 3;
+	unsigned t[12];
+#pragma unroll
+	for (int q = 0; q < 6; ++q) { t[q] = p00[q]; t[6 + q] = p10[q]; }
+	const float a0 = byte_pixel(t[0]), a1 = byte_pixel(t[1]), a2 = byte_pixel(t[2]);
+	const float d0 = byte_pixel(t[3]), d1 = byte_pixel(t[4]), d2 = byte_pixel(t[5]);
+	const float b0 = byte_pixel(t[6]), b1 = byte_pixel(t[7]), b2 = byte_pixel(t[8]);
+	const float c0 = byte_pixel(t[9]), c1 = byte_pixel(t[10]), c2 = byte_pixel(t[11]);
+	float w = (1 - r) * (1 - c);
+	float r0 = 0.f + a0 * w, r1 = 0.f + a1 * w, r2 = 0.f + a2 * w;
+	w = r * (1 - c);
+	r0 += b0 * w; r1 += b1 * w; r2 += b2 * w;
+	w = r * c;
+	r0 += c0 * w; r1 += c1 * w; r2 += c2 * w;
+	w = (1 - r) * c;
+	r0 += d0 * w; r1 += d1 * w; r2 += d2 * w;
+	out[0] = r0; out[1] = r1; out[2] = r2;
+	return true;
+}
+
+__device__ __forceinline__ bool source_interpolate(const float* img, int rows, int cols, float r, float c, float (&out)[3]) { return interpolate(img, rows, cols, r, c, out); }
+__device__ __forceinline__ bool source_interpolate(const unsigned char* img, int rows, int cols, float r, float c, float (&out)[3]) { return interpolate_u8(img, rows, cols, r, c, out); }
+
+// The one place the blend kernels read a source image.  U8: the instance of a call whose set holds a byte view -- the
+// type is per image, and the walk over covering images is wave-uniform, so the branch is too; an all-fp32 call runs the
+// instance without it.
+template <bool U8>
+__device__ __forceinline__ bool sample_source(const BlendImg& im, float r, float c, float (&out)[3]) {
+	if (U8 && im.u8) return interpolate_u8((const unsigned char*)im.data, im.mh, im.mw, r, c, out);
+	return interpolate((const float*)im.data, im.mh, im.mw, r, c, out);
 }
 
 // The canvas-pixel kernels below walk "every image whose ROI holds this pixel, in index order".  Testing all n ROIs per
@@ -137,6 +200,7 @@ __device__ __forceinline__ void walk_cover(const unsigned long long* s_cover, in
 // the ROI test of the branch (non-lazy: Range::contain, inclusive, blender.cc:84; lazy: the loops exclude max,
 // blender.cc:49-51), ImageToAdd::map_coor (blender.hh:39-44), interpolate() != NO and col[0] >= 0.  false = the image
 // adds nothing here.  r / c: the sample's image coordinates (the blend weight's operands).
+template <bool U8>
 __device__ __forceinline__ bool linear_sample(const BlendImg& im, int i, int j, double hx, double hy, double hz, int lazy,
 		float& r, float& c, float (&col)[3]) {
 	const bool in = lazy ? (i >= im.y0 && i < im.y1 && j >= im.x0 && j < im.x1)
@@ -146,7 +210,7 @@ __device__ __forceinline__ bool linear_sample(const BlendImg& im, int i, int j, 
 	space_to_image(im, hx, hy, hz, ox, oy);
 	if (ox < 0 || ox >= im.w || oy < 0 || oy >= im.h) return false;
 	r = (float)oy; c = (float)ox;
-	if (!interpolate(im.data, im.mh, im.mw, r, c, col)) return false;
+	if (!sample_source<U8>(im, r, c, col)) return false;
 	return !(col[0] < 0);
 }
 
@@ -231,7 +295,7 @@ __device__ __forceinline__ void apply_gain_mode(const float* __restrict__ gains,
 // (n x 3) scale every sample (op_blend_gains); GAIN_BLOCK -- gains (n x gby x gbx x 3) are interpolated at the sample
 // (op_blend_block_gains); GAIN_VIGNETTE -- gains (n x 3, then the curve's a1..a3 at gains + 3n) are divided by the shared
 // curve at the sample (op_blend_vignette); GAIN_NONE -- the kernel is op_blend's.  gbx / gby are read by GAIN_BLOCK only ----
-template <int GM>
+template <int GM, bool U8>
 __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		float* __restrict__ out, int H, int W, int ordered_input, int lazy, const float* __restrict__ gains, int gbx, int gby) {
 	__shared__ unsigned long long s_cover[COVER_WORDS];
@@ -247,7 +311,7 @@ __global__ void __launch_bounds__(256) k_blend_linear(BlendGeom g, BlendTrig tri
 		walk_cover(s_cover, k0, n, [&](int k) {
 			const BlendImg& im = imgs[k];
 			float r, c, col[3];
-			if (!linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col)) return;
+			if (!linear_sample<U8>(im, i, j, hx, hy, hz, lazy, r, c, col)) return;
 			apply_gain_mode<GM>(gains, k, n, gbx, gby, im.w, im.h, r, c, col);
 			float w = (float)(0.5 - fabs((double)(c / (float)im.w) - 0.5));
 			if (!ordered_input) w = (float)((double)w * (0.5 - fabs((double)(r / (float)im.h) - 0.5)));
@@ -305,7 +369,7 @@ __host__ __device__ __forceinline__ long long pair_index(int a, int b, int n) { 
 // struct of the arrays, leaves the chunk in scratch memory).  S::clear(p1, p2): the slot without a sample.  S::sample(p1, p2,
 // im, lin): the slot of image im, where lin(im, r, c, col) is linear_sample at this lattice point; false: no valid sample,
 // or one the statistic refuses.  S::pair(a, b, n, va, p1a, p2a, vb, p1b, p2b): the statistic of the pair (a < b).
-template <typename S>
+template <bool U8, typename S>
 __device__ __forceinline__ void overlap_walk(const BlendGeom& g, const BlendTrig& trig, const BlendImg* imgs, int n,
 		int H, int W, int stride, int lazy, const S& stat) {
 	extern __shared__ unsigned long long s_gcover[];
@@ -328,7 +392,7 @@ __device__ __forceinline__ void overlap_walk(const BlendGeom& g, const BlendTrig
 	}
 	double hx, hy, hz;
 	proj2homo(g, trig, i, j, hx, hy, hz);
-	auto lin = [&](const BlendImg& im, float& r, float& c, float (&col)[3]) { return live && linear_sample(im, i, j, hx, hy, hz, lazy, r, c, col); };
+	auto lin = [&](const BlendImg& im, float& r, float& c, float (&col)[3]) { return live && linear_sample<U8>(im, i, j, hx, hy, hz, lazy, r, c, col); };
 	int a0 = next_cover(s_gcover, words, 0);
 	while (a0 < n) {
 		int ka[GAIN_CH]; bool va[GAIN_CH]; typename S::P1 p1a[GAIN_CH]; typename S::P2 p2a[GAIN_CH];
@@ -389,9 +453,10 @@ struct GainStat {                                       // a slot: the colour
 		gain_pair(a, b, n, va, x, vb, y, count, sums);
 	}
 };
+template <bool U8>
 __global__ void __launch_bounds__(256) k_gain_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		int H, int W, int stride, int lazy, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
-	overlap_walk(g, trig, imgs, n, H, W, stride, lazy, GainStat{count, sums});
+	overlap_walk<U8>(g, trig, imgs, n, H, W, stride, lazy, GainStat{count, sums});
 }
 
 // ---- block statistics for op_gain_block_overlap: k_gain_overlap with every slot also carrying its sample's block
@@ -444,9 +509,10 @@ struct GainBlockStat {                                  // a slot: the colour an
 		gain_block_pair(a, b, n, bx * by, va, qa, x, vb, qb, y, count, sums);
 	}
 };
+template <bool U8>
 __global__ void __launch_bounds__(256) k_gain_block_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		int H, int W, int stride, int lazy, int bx, int by, unsigned long long* __restrict__ count, unsigned long long* __restrict__ sums) {
-	overlap_walk(g, trig, imgs, n, H, W, stride, lazy, GainBlockStat{bx, by, count, sums});
+	overlap_walk<U8>(g, trig, imgs, n, H, W, stride, lazy, GainBlockStat{bx, by, count, sums});
 }
 
 // ---- vignetting statistics for op_vignette_overlap: every slot carries the grey level Y and the radius rho of its sample
@@ -502,9 +568,10 @@ struct VignetteStat {                                   // a slot: the grey leve
 		vignette_pair(a, b, n, va, ya, ra, vb, yb, rb, count, moments);
 	}
 };
+template <bool U8>
 __global__ void __launch_bounds__(256) k_vignette_overlap(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		int H, int W, int stride, int lazy, float clip, unsigned long long* __restrict__ count, unsigned long long* __restrict__ moments) {
-	overlap_walk(g, trig, imgs, n, H, W, stride, lazy, VignetteStat{clip, count, moments});
+	overlap_walk<U8>(g, trig, imgs, n, H, W, stride, lazy, VignetteStat{clip, count, moments});
 }
 
 // ---- create_first_level + update_weight_map (multiband.cc:19-56,125-143) in ONE pass, thread per canvas pixel:
@@ -517,7 +584,7 @@ __global__ void __launch_bounds__(256) k_vignette_overlap(BlendGeom g, BlendTrig
 // GM (as k_blend_linear's): the level-0 colours are the gained samples (op_blend_gains, op_blend_block_gains -- the block
 // gain interpolated at the floats interpolate() reads; op_blend_vignette -- the curve at those floats); the weights do not
 // depend on colour.
-template <int GM>
+template <int GM, bool U8>
 __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig trig, const BlendImg* __restrict__ imgs, int n,
 		float4* __restrict__ cur, unsigned char* __restrict__ mask, float* __restrict__ out, unsigned char* __restrict__ tmask, int H, int W,
 		const float* __restrict__ gains, int gbx, int gby) {
@@ -543,7 +610,7 @@ __global__ void __launch_bounds__(256) k_mb_first_fused(BlendGeom g, BlendTrig t
 			double ox, oy;
 			space_to_image(im, hx, hy, hz, ox, oy);
 			float col[3];
-			bool ok = interpolate(im.data, im.mh, im.mw, (float)oy, (float)ox, col);
+			bool ok = sample_source<U8>(im, (float)oy, (float)ox, col);
 			if (ok) { float mn = fminf(col[0], fminf(col[1], col[2])); if (mn < 0) ok = false; }
 			if (ok) apply_gain_mode<GM>(gains, k, n, gbx, gby, im.w, im.h, (float)oy, (float)ox, col);
 			float4 px = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -815,7 +882,8 @@ __global__ void __launch_bounds__(256) k_mb_bands(const BlendImg* __restrict__ i
 // ---- CylinderProject::project (stitch/warp.cc:25-44): thread per output pixel ----
 // coltc[j] = (tan, cos) of the column's angle (j - offset.x) * sizefactor_inv, from the host libm (cyl_tables below)
 struct CylParams { double cx, cy, offx, offy, sizefactor_inv; int r; };
-__global__ void __launch_bounds__(256) k_cyl_project(CylParams P, const double2* __restrict__ coltc, const float* __restrict__ img, int h, int w,
+template <typename T>       // T: float (Mat32f) or unsigned char (decoder bytes, interpolate_u8)
+__global__ void __launch_bounds__(256) k_cyl_project(CylParams P, const double2* __restrict__ coltc, const T* __restrict__ img, int h, int w,
 		float* __restrict__ out, int nh, int nw) {
 	const int j = blockIdx.x * 64 + (threadIdx.x & 63);
 	const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -827,7 +895,7 @@ __global__ void __launch_bounds__(256) k_cyl_project(CylParams P, const double2*
 	float c[3] = {-1.f, -1.f, -1.f};
 	// between(a, b, c) = a >= b && a <= c - 1 (lib/utils.hh:27)
 	if (ox >= 0 && ox <= (double)(w - 1) && oy >= 0 && oy <= (double)(h - 1))
-		interpolate(img, h, w, (float)oy, (float)ox, c);
+		source_interpolate(img, h, w, (float)oy, (float)ox, c);
 	float* p = out + ((long long)i * nw + j) * 3;
 	p[0] = c[0]; p[1] = c[1]; p[2] = c[2];
 }
@@ -1160,6 +1228,8 @@ int upload_images(op_ctx* ctx, const char* who, const op_blend_geom* g, const op
 	const std::string w = who;
 	h_imgs.assign(n, BlendImg{});
 	roi_total = 0; max_roi = 0;
+	for (int k = 0; k < n; ++k)       // the flag word, before any device work
+		if (imgs[k].on_device & ~(OP_SRC_DEVICE | OP_SRC_U8)) OP_FAIL(OP_ERR_INVALID, w + ": unknown source flag on image " + std::to_string(k));
 	for (int k = 0; k < n; ++k) {
 		const op_blend_image& s = imgs[k];
 		if (!s.data || s.h < 2 || s.w < 2) OP_FAIL(OP_ERR_INVALID, w + ": bad image " + std::to_string(k));
@@ -1167,11 +1237,13 @@ int upload_images(op_ctx* ctx, const char* who, const op_blend_geom* g, const op
 		b.h = s.h; b.w = s.w;
 		b.mh = s.mat_h > 0 ? s.mat_h : s.h; b.mw = s.mat_w > 0 ? s.mat_w : s.w;
 		if (b.mh < 2 || b.mw < 2) OP_FAIL(OP_ERR_INVALID, w + ": bad pixel buffer size of image " + std::to_string(k));
-		if (s.on_device) b.data = s.data;
-		else {
-			float* d = nullptr;
-			HIPCHK(pool_alloc((void**)&d, sizeof(float) * 3 * (size_t)b.mh * b.mw)); fr.v.push_back(d);
-			HIPCHK(hipMemcpyAsync(d, s.data, sizeof(float) * 3 * (size_t)b.mh * b.mw, hipMemcpyHostToDevice, st));
+		b.u8 = (s.on_device & OP_SRC_U8) ? 1 : 0;
+		if (s.on_device & OP_SRC_DEVICE) b.data = s.data;
+		else {            // a host view goes up in the type it has: 3 h w bytes, or 12 h w
+			const size_t bytes = (b.u8 ? 1 : sizeof(float)) * 3 * (size_t)b.mh * b.mw;
+			void* d = nullptr;
+			HIPCHK(pool_alloc(&d, bytes)); fr.v.push_back(d);
+			HIPCHK(hipMemcpyAsync(d, s.data, bytes, hipMemcpyHostToDevice, st));
 			b.data = d;
 		}
 		int roi[4]; roi_of(g, s.range, roi);
@@ -1241,10 +1313,14 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 #define BCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
 	pool_free(cv->data); delete cv; return OP_ERR_HIP; } } while (0)
 	// the instances of the gain mode (gbx / gby are read by GAIN_BLOCK only)
-	auto linear = k_blend_linear<GAIN_NONE>; auto first = k_mb_first_fused<GAIN_NONE>;
-	if (gm == GAIN_IMAGE) { linear = k_blend_linear<GAIN_IMAGE>; first = k_mb_first_fused<GAIN_IMAGE>; }
-	else if (gm == GAIN_BLOCK) { linear = k_blend_linear<GAIN_BLOCK>; first = k_mb_first_fused<GAIN_BLOCK>; }
-	else if (gm == GAIN_VIGNETTE) { linear = k_blend_linear<GAIN_VIGNETTE>; first = k_mb_first_fused<GAIN_VIGNETTE>; }
+	// and of the set's source types: the byte sampler is compiled into the U8 instances only, an all-fp32 call runs the others
+	bool any_u8 = false;
+	for (const BlendImg& b : h_imgs) any_u8 = any_u8 || b.u8;
+	auto linear = k_blend_linear<GAIN_NONE, false>; auto first = k_mb_first_fused<GAIN_NONE, false>;
+#define OP_GM_CASE(M) if (gm == M) { linear = any_u8 ? k_blend_linear<M, true> : k_blend_linear<M, false>; \
+	first = any_u8 ? k_mb_first_fused<M, true> : k_mb_first_fused<M, false>; }
+	OP_GM_CASE(GAIN_NONE) OP_GM_CASE(GAIN_IMAGE) OP_GM_CASE(GAIN_BLOCK) OP_GM_CASE(GAIN_VIGNETTE)
+#undef OP_GM_CASE
 	if (cfg->MULTIBAND <= 0) {
 		ProfScope ps(ctx, "blend linear");
 		hipLaunchKernelGGL(linear, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
@@ -1354,10 +1430,10 @@ int check_gains(const char* who, const float* gains, long long count, long long 
 // The host side of op_gain_overlap, op_gain_block_overlap and op_vignette_overlap after their own checks: `entries` counts
 // and entries x per values, zeroed on the device, filled by kernel(bg, trig, images, n, H, W, stride, LAZY_READ, extra...,
 // counts, values) over the canvas lattice of `stride`, copied to count / values.  cap_lattice: more than VIG_MAX_LATTICE
-// lattice points are refused (the bound of the vignetting sums).
+// lattice points are refused (the bound of the vignetting sums).  kernel_u8: the instance for a set that holds a byte view.
 template <typename K, typename... X>
 int overlap_stats(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride, const char* who,
-		const char* label, long long entries, int per, bool cap_lattice, int64_t* count, int64_t* values, K kernel, X... extra) {
+		const char* label, long long entries, int per, bool cap_lattice, int64_t* count, int64_t* values, K kernel, K kernel_u8, X... extra) {
 	if (entries == 0) return OP_OK;                     // one image: no pair
 	HIPCHK(hipSetDevice(ctx->device));
 	hipStream_t st = ctx->stream;
@@ -1386,8 +1462,10 @@ int overlap_stats(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, con
 		HostScope hs(ctx, "blend trig tables (host)");
 		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
 	}
+	bool any_u8 = false;
+	for (const BlendImg& b : h_imgs) any_u8 = any_u8 || b.u8;
 	{ ProfScope ps(ctx, label);
-	  hipLaunchKernelGGL(kernel, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * ((n + 63) / 64), st,
+	  hipLaunchKernelGGL(any_u8 ? kernel_u8 : kernel, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * ((n + 63) / 64), st,
 	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, extra..., d_stats, d_stats + entries);
 	  HIPCHK(hipGetLastError()); }
 	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)entries, hipMemcpyDeviceToHost, st));
@@ -1447,7 +1525,7 @@ int op_vignette_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* 
 	if (rc != OP_OK) return rc;
 	if (n > GAIN_MAX_IMAGES) OP_FAIL(OP_ERR_UNSUPPORTED, "op_vignette_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
 	return overlap_stats(ctx, cfg, g, imgs, n, stride, "op_vignette_overlap", "vignette overlap", (long long)n * (n - 1) / 2, VIG_MOMENTS, true,
-	                     count, moments, k_vignette_overlap, clip);
+	                     count, moments, k_vignette_overlap<false>, k_vignette_overlap<true>, clip);
 }
 
 int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const op_blend_image* imgs, int n, int stride,
@@ -1458,7 +1536,7 @@ int op_gain_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, c
 	if (rc != OP_OK) return rc;
 	if (n > GAIN_MAX_IMAGES) OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_overlap: more than " + std::to_string(GAIN_MAX_IMAGES) + " images");
 	return overlap_stats(ctx, cfg, g, imgs, n, stride, "op_gain_overlap", "gain overlap", (long long)n * (n - 1) / 2, 6, false,
-	                     count, sums, k_gain_overlap);
+	                     count, sums, k_gain_overlap<false>, k_gain_overlap<true>);
 }
 
 }	// extern "C"
@@ -1609,7 +1687,7 @@ int op_gain_block_overlap(op_ctx* ctx, const op_config* cfg, const op_blend_geom
 		OP_FAIL(OP_ERR_UNSUPPORTED, "op_gain_block_overlap: " + std::to_string(entries) + " unit-pair entries (pairs x (bx by)^2) exceed " +
 		        std::to_string(GAIN_BLOCK_MAX_ENTRIES));
 	return overlap_stats(ctx, cfg, g, imgs, n, stride, "op_gain_block_overlap", "gain block overlap", entries, 6, false, count, sums,
-	                     k_gain_block_overlap, bx, by);
+	                     k_gain_block_overlap<false>, k_gain_block_overlap<true>, bx, by);
 }
 
 // Block gain compensation, host only: op_gain_solve's normal equations over units (k, q) -- entry e = p B^2 + qa B + qb
@@ -1861,12 +1939,14 @@ int op_cyl_warp(op_ctx* ctx, const op_config* cfg, const op_image* img, double h
 	if (rc != OP_OK) return rc;
 	if (nw <= 0 || nh <= 0) OP_FAIL(OP_ERR_INVALID, "op_cyl_warp: empty output");
 	Freer fr;
-	if (img->dtype != OP_F32) OP_FAIL(OP_ERR_UNSUPPORTED, "op_cyl_warp: fp32 images only");
-	const float* src = (const float*)img->data;
+	if (img->dtype != OP_F32 && img->dtype != OP_U8) OP_FAIL(OP_ERR_INVALID, "op_cyl_warp: unknown dtype");
+	const bool u8 = img->dtype == OP_U8;
+	const void* src = img->data;
 	if (!img->on_device) {
-		float* d = nullptr;
-		HIPCHK(pool_alloc((void**)&d, sizeof(float) * 3 * (size_t)img->h * img->w)); fr.v.push_back(d);
-		HIPCHK(hipMemcpyAsync(d, img->data, sizeof(float) * 3 * (size_t)img->h * img->w, hipMemcpyHostToDevice, st));
+		const size_t bytes = (u8 ? 1 : sizeof(float)) * 3 * (size_t)img->h * img->w;
+		void* d = nullptr;
+		HIPCHK(pool_alloc(&d, bytes)); fr.v.push_back(d);
+		HIPCHK(hipMemcpyAsync(d, img->data, bytes, hipMemcpyHostToDevice, st));
 		src = d;
 	}
 	const CylProj P = cyl_projector(img->w, img->h, h_factor, cfg->FOCAL_LENGTH);
@@ -1878,13 +1958,85 @@ int op_cyl_warp(op_ctx* ctx, const op_config* cfg, const op_image* img, double h
 	{ hipError_t e = cyl_tables(ctx, cp.offx, cp.sizefactor_inv, nw, &coltc);
 	  if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string("op_cyl_warp: trig table: ") + hipGetErrorString(e)); } }
 	{ ProfScope ps(ctx, "cylinder warp");
-	  hipLaunchKernelGGL(k_cyl_project, dim3((nw + 63) / 64, (nh + 3) / 4), dim3(256), 0, st, cp, coltc, src, img->h, img->w, cv->data, nh, nw); }
+	  if (u8) hipLaunchKernelGGL(k_cyl_project<unsigned char>, dim3((nw + 63) / 64, (nh + 3) / 4), dim3(256), 0, st, cp, coltc, (const unsigned char*)src, img->h, img->w, cv->data, nh, nw);
+	  else hipLaunchKernelGGL(k_cyl_project<float>, dim3((nw + 63) / 64, (nh + 3) / 4), dim3(256), 0, st, cp, coltc, (const float*)src, img->h, img->w, cv->data, nh, nw); }
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
 	if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string("op_cyl_warp: ") + hipGetErrorString(e)); }
 	resolve_profile(ctx);
 	*out = cv;
 	return OP_OK;
+}
+
+// ---- op_views: the views of a job, uploaded once in the type the decoder produced, resident for SIFT, the cylinder
+// warp, the overlap passes and every blend (the reference's seam: ImageRef::load / img, stitch/imageref.hh:15-31) ----
+int op_views_upload(op_ctx* ctx, const op_image* imgs, int n, op_views** out) {
+	if (!ctx || !imgs || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_views_upload: bad argument");
+	*out = nullptr;
+	for (int i = 0; i < n; ++i)
+		if (!imgs[i].data || imgs[i].h < 2 || imgs[i].w < 2 || (imgs[i].dtype != OP_F32 && imgs[i].dtype != OP_U8) ||
+				(imgs[i].on_device != 0 && imgs[i].on_device != 1))
+			OP_FAIL(OP_ERR_INVALID, "op_views_upload: bad image " + std::to_string(i));
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	// every view at an offset that is a multiple of 256 bytes of ONE block
+	std::vector<size_t> bytes(n), off(n);
+	size_t total = 0;
+	for (int i = 0; i < n; ++i) {
+		bytes[i] = (imgs[i].dtype == OP_U8 ? 1 : sizeof(float)) * 3 * (size_t)imgs[i].h * imgs[i].w;
+		off[i] = total; total += (bytes[i] + 255) & ~(size_t)255;
+	}
+	char* block = nullptr;
+	HIPCHK(pool_alloc((void**)&block, total));
+	// host images of one size at one constant stride (a contiguous array of frames, a decoder pool) go up in ONE copy
+	bool packed = n > 1;
+	for (int i = 0; i < n && packed; ++i) packed = !imgs[i].on_device && bytes[i] == bytes[0];
+	ptrdiff_t hstride = packed ? (const char*)imgs[1].data - (const char*)imgs[0].data : 0;
+	packed = packed && hstride >= (ptrdiff_t)bytes[0];
+	for (int i = 2; i < n && packed; ++i) packed = (const char*)imgs[i].data - (const char*)imgs[i - 1].data == hstride;
+	hipError_t e = hipSuccess;
+	if (packed) e = hipMemcpy2DAsync(block, off[1], imgs[0].data, (size_t)hstride, bytes[0], (size_t)n, hipMemcpyHostToDevice, st);
+	else for (int i = 0; i < n && e == hipSuccess; ++i)
+		e = hipMemcpyAsync(block + off[i], imgs[i].data, bytes[i], imgs[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);       // the caller's host buffers are free again when this returns
+	if (e != hipSuccess) { pool_free(block); OP_FAIL(OP_ERR_HIP, std::string("op_views_upload: ") + hipGetErrorString(e)); }
+	op_views* v = new op_views;
+	v->ctx = ctx; v->block = block;
+	v->imgs.resize(n);
+	for (int i = 0; i < n; ++i) v->imgs[i] = op_image{block + off[i], imgs[i].h, imgs[i].w, 1, imgs[i].dtype};
+	*out = v;
+	return OP_OK;
+}
+
+int op_views_count(const op_views* v) {
+	if (!v) OP_FAIL(OP_ERR_INVALID, "op_views_count: NULL views");
+	return (int)v->imgs.size();
+}
+
+int op_views_image(const op_views* v, int i, op_image* out) {
+	if (!v || !out || i < 0 || i >= (int)v->imgs.size()) OP_FAIL(OP_ERR_INVALID, "op_views_image: bad argument");
+	*out = v->imgs[i];
+	return OP_OK;
+}
+
+int op_views_blend_image(const op_views* v, int i, op_blend_image* out) {
+	if (!v || !out || i < 0 || i >= (int)v->imgs.size()) OP_FAIL(OP_ERR_INVALID, "op_views_blend_image: bad argument");
+	const op_image& im = v->imgs[i];
+	out->data = (const float*)im.data; out->h = im.h; out->w = im.w;
+	out->on_device = OP_SRC_DEVICE | (im.dtype == OP_U8 ? OP_SRC_U8 : 0);
+	out->mat_h = 0; out->mat_w = 0;
+	return OP_OK;
+}
+
+void op_views_free(op_views* v) {
+	if (!v) return;
+	// the pool does not track streams: work of the context's stream that still reads the views must be over before the
+	// block can be handed to another caller
+	if (v->block) {
+		if (hipSetDevice(v->ctx->device) == hipSuccess) (void)hipStreamSynchronize(v->ctx->stream);
+		pool_free(v->block);
+	}
+	delete v;
 }
 
 }	// extern "C"

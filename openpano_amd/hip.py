@@ -50,6 +50,7 @@ class OpImage(C.Structure):
 
 
 OP_F32, OP_U8 = 0, 1
+OP_SRC_DEVICE, OP_SRC_U8 = 1, 2        # bits of op_blend_image.on_device
 
 
 class OpBlendImage(C.Structure):
@@ -228,6 +229,12 @@ def lib():
     L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
+    if hasattr(L, "op_views_upload"):
+        L.op_views_upload.argtypes = [C.c_void_p, C.POINTER(OpImage), C.c_int, C.POINTER(C.c_void_p)]
+        L.op_views_count.argtypes = [C.c_void_p]
+        L.op_views_image.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpImage)]
+        L.op_views_blend_image.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpBlendImage)]
+        L.op_views_free.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -365,6 +372,73 @@ def _mk_images(images):
                 raise ValueError("image must be H x W x 3 (float32 or uint8)")
             keep.append(a)
             arr[i] = OpImage(a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], 0, OP_U8 if a.dtype == np.uint8 else OP_F32)
+    return arr, keep
+
+
+class Views:
+    """``op_views``: the views of a job uploaded once, each in the type it arrived in (float32, or uint8 decoder bytes),
+    resident for ``sift_batch`` / ``cyl_warp`` (``images()``) and for ``blend`` and the overlap passes (pass the object, or
+    ``blend_images()``).  The seam of ImageRef::load / img (stitch/imageref.hh:15-31)."""
+
+    def __init__(self, ctx: Context, handle):
+        self.ctx = ctx
+        self.handle = handle
+
+    @classmethod
+    def upload(cls, ctx: Context, images) -> "Views":
+        """images: as ``sift_batch`` takes them (numpy HWC float32 / uint8, or device tuples); one copy for a
+        contiguous stack of host frames"""
+        arr, keep = _mk_images(images)
+        h = C.c_void_p()
+        check(lib().op_views_upload(ctx.handle, arr, len(images), C.byref(h)))
+        del keep
+        return cls(ctx, h)
+
+    @property
+    def count(self):
+        return lib().op_views_count(self.handle)
+
+    def __len__(self):
+        return self.count
+
+    def images(self):
+        """device tuples (ptr, h, w[, "u8"]) for sift_batch / cyl_warp; valid until free()"""
+        out = []
+        for i in range(self.count):
+            im = OpImage()
+            check(lib().op_views_image(self.handle, i, C.byref(im)))
+            out.append((im.data, im.h, im.w, "u8") if im.dtype == OP_U8 else (im.data, im.h, im.w))
+        return out
+
+    def blend_images(self):
+        """an ``op_blend_image`` array with data, h, w and the source flags filled (homo_inv / range zero)"""
+        arr = (OpBlendImage * self.count)()
+        for i in range(self.count):
+            check(lib().op_views_blend_image(self.handle, i, C.byref(arr[i])))
+        return arr
+
+    def free(self):
+        if self.handle:
+            lib().op_views_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _mk_blend_images(images):
+    """the sources of a blend as an ``op_blend_image`` array (data, h, w, flag word): a ``Views``, or a list of numpy HWC
+    arrays (float32, or uint8 decoder bytes: OP_SRC_U8) and device tuples (ptr, h, w) / (ptr, h, w, "u8")"""
+    if isinstance(images, Views):
+        return images.blend_images(), images
+    arr_img, keep = _mk_images(images)
+    arr = (OpBlendImage * len(images))()
+    for i in range(len(images)):
+        arr[i].data = arr_img[i].data; arr[i].h = arr_img[i].h; arr[i].w = arr_img[i].w
+        arr[i].on_device = (OP_SRC_DEVICE if arr_img[i].on_device else 0) | (OP_SRC_U8 if arr_img[i].dtype == OP_U8 else 0)
     return arr, keep
 
 
@@ -865,17 +939,17 @@ class BlendCall:
     once, like a C host holds them; every call is one op_blend -- or, with ``gains`` ((n, 3) or (n,) exposure gains), one
     op_blend_gains; with (n, by, bx, 3) block gains, one op_blend_block_gains; with ``vignette`` (a1, a2, a3: the shared
     curve of op_vignette_solve), one op_blend_vignette of ``gains`` ((n, 3), (n,) or None = 1).
-    images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo."""
+    images: numpy HWC float32 or uint8 (decoder bytes) arrays, (device_ptr, h, w) / (device_ptr, h, w, "u8") tuples, or a
+    ``Views``; byte sources are converted in the sampler (OP_SRC_U8).  homos: n x 3 x 3 ImageComponent::homo."""
 
     def __init__(self, ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None, vignette=None):
         self.ctx = ctx
         n = self.n = len(images)
-        arr_img, self._keep = _mk_images(images)
-        shapes = [(arr_img[i].w, arr_img[i].h) for i in range(n)]
+        arr, self._keep = _mk_blend_images(images)
+        self.arr = arr
+        shapes = [(arr[i].w, arr[i].h) for i in range(n)]
         self.geom, hinv, ranges = blend_prepare(cfg, shapes, homos, proj_method, identity_idx)
-        arr = self.arr = (OpBlendImage * n)()
         for i in range(n):
-            arr[i].data = arr_img[i].data; arr[i].h = arr_img[i].h; arr[i].w = arr_img[i].w; arr[i].on_device = arr_img[i].on_device
             for k in range(9):
                 arr[i].homo_inv[k] = hinv[i, k]
             for k in range(4):
@@ -943,7 +1017,8 @@ class BlendCall:
 
 def blend(ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None, vignette=None) -> Canvas:
     """``ConnectedImages::blend()`` (stitcher_image.cc:116-155) on the device.
-    images: numpy HWC float32 arrays or (device_ptr, h, w); homos: n x 3 x 3 ImageComponent::homo.
+    images: numpy HWC float32 / uint8 arrays, device tuples (ptr, h, w[, "u8"]) or a ``Views``; homos: n x 3 x 3
+    ImageComponent::homo.
     gains: optional (n, 3) or (n,) exposure gains (op_blend_gains), or (n, by, bx, 3) block gains (op_blend_block_gains);
     None = op_blend.  vignette: optional (a1, a2, a3), the shared curve of vignette_solve (op_blend_vignette, with gains)."""
     return BlendCall(ctx, cfg, images, homos, proj_method, identity_idx, gains=gains, vignette=vignette)()
@@ -1045,6 +1120,7 @@ def cyl_warp_shape(cfg, w, h, h_factor, pts=None):
 
 
 def cyl_warp(ctx: Context, cfg, image, h_factor) -> Canvas:
+    """``CylinderWarper::warp``'s pixels; image: float32, or uint8 decoder bytes (host array or device tuple)"""
     arr, keep = _mk_images([image])
     ccfg = OpConfig.from_config(cfg)
     h = C.c_void_p()

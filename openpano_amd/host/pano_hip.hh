@@ -159,13 +159,22 @@ class FeatureDetector {
 // op_features handle so that the matcher does not re-upload descriptors
 struct HipFeatureSet {
 	op_features* handle = nullptr;
+	// the images themselves, resident on the device in the type they were uploaded in (calc_feature with resident_views):
+	// the blend and the overlap passes read them there instead of a second, fp32 upload (ConnectedImages::views)
+	op_views* views = nullptr;
 	std::vector<std::vector<Descriptor>> feats;     // centred coordinates, like StitcherBase::feats
 	HipFeatureSet() = default;
 	HipFeatureSet(const HipFeatureSet&) = delete;
 	HipFeatureSet& operator=(const HipFeatureSet&) = delete;
-	HipFeatureSet(HipFeatureSet&& o): handle(o.handle), feats(std::move(o.feats)) { o.handle = nullptr; }
-	HipFeatureSet& operator=(HipFeatureSet&& o) { if (this != &o) { op_features_free(handle); handle = o.handle; feats = std::move(o.feats); o.handle = nullptr; } return *this; }
-	~HipFeatureSet() { op_features_free(handle); }
+	HipFeatureSet(HipFeatureSet&& o): handle(o.handle), views(o.views), feats(std::move(o.feats)) { o.handle = nullptr; o.views = nullptr; }
+	HipFeatureSet& operator=(HipFeatureSet&& o) {
+		if (this != &o) {
+			op_features_free(handle); op_views_free(views);
+			handle = o.handle; views = o.views; feats = std::move(o.feats); o.handle = nullptr; o.views = nullptr;
+		}
+		return *this;
+	}
+	~HipFeatureSet() { op_features_free(handle); op_views_free(views); }
 };
 
 class HipSIFTDetector PANO_DETECTOR_BASE {
@@ -196,7 +205,10 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 
 		// StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27) as ONE batched device call:
 		// all images in one launch series, descriptors left resident for the matcher.
-		HipFeatureSet calc_feature(const std::vector<const Mat32f*>& imgs) const {
+		// resident_views: the images go up ONCE as an op_views kept in the result (bytes when every pixel is an exact k / 255,
+		// fp32 otherwise), SIFT reads them there, and so do the blend and the overlap passes of a bundle whose `views` is set
+		// to it.  Ignored with a device group, whose images are dealt over several GPUs.
+		HipFeatureSet calc_feature(const std::vector<const Mat32f*>& imgs, bool resident_views = false) const {
 			op_ctx* ctx = HipContext::get();
 			const op_config cfg = hip_config_snapshot();
 			std::vector<op_image> ims;
@@ -247,6 +259,17 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 			if (op_group* g = HipContext::group()) {        // images dealt over the group's GPUs, features all-gathered
 				PANO_HIP_CHECK(op_sift_batch_multi(g, &cfg, ims.data(), (int)ims.size(), &fs.handle));
 				ctx = op_group_ctx(g, 0);
+				const size_t total = (size_t)op_features_total(fs.handle);
+				desc.resize(total * 128 + 1); coor.resize(total * 2 + 1);
+				for (size_t k = 0; k < imgs.size(); ++k)
+					if (op_features_count(fs.handle, (int)k))
+						PANO_HIP_CHECK(op_features_copy(ctx, fs.handle, (int)k, desc.data() + (size_t)op_features_offset(fs.handle, (int)k) * 128,
+								coor.data() + (size_t)op_features_offset(fs.handle, (int)k) * 2));
+			} else if (resident_views) {
+				PANO_HIP_CHECK(op_views_upload(ctx, ims.data(), (int)ims.size(), &fs.views));
+				std::vector<op_image> dev(ims.size());
+				for (size_t k = 0; k < ims.size(); ++k) PANO_HIP_CHECK(op_views_image(fs.views, (int)k, &dev[k]));
+				PANO_HIP_CHECK(op_sift_batch(ctx, &cfg, dev.data(), (int)dev.size(), &fs.handle));
 				const size_t total = (size_t)op_features_total(fs.handle);
 				desc.resize(total * 128 + 1); coor.resize(total * 2 + 1);
 				for (size_t k = 0; k < imgs.size(); ++k)
@@ -569,6 +592,9 @@ struct ConnectedImages {
 		ImageComponent(ImageRef* img): imgptr(img) {}
 	};
 	std::vector<ImageComponent> component;
+	// Optional: the components' images, in component order, resident on the device (HipFeatureSet::views; not owned).  The
+	// blend and the overlap passes then read view i for component i instead of uploading imgptr->img (hip_blend_images).
+	const op_views* views = nullptr;
 	// stitcher_image.cc:36-77: homo_inv from homo; ranges / proj_range / resolution from homo.  Kept
 	// separate like the reference's: Stitcher::estimate_camera sets homo_inv = K R itself and only
 	// calls update_proj_range() (stitcher.cc:154-158, :59)
@@ -608,6 +634,9 @@ inline op_blend_geom hip_blend_prepare(const Bundle& b, std::vector<double>& hin
 // Exposure (gain) compensation -- an extension beyond the reference (Brown & Lowe, IJCV 2007, section 6; the C-ABI's
 // op_gain_overlap + op_gain_solve): the n x 3 gains that equalise the bundle's overlaps, from the samples the linear
 // blender takes on the canvas lattice of the given stride.  Pass them to hip_blend(b, crop, gains).
+// the bundle's resident views, when it has the member (the reference's ConnectedImages has none)
+template <typename Bundle> inline auto hip_bundle_views(const Bundle& b, int) -> decltype(b.views) { return b.views; }
+template <typename Bundle> inline const op_views* hip_bundle_views(const Bundle&, long) { return nullptr; }
 template <typename Bundle>
 inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_geom& g) {
 	const int n = (int)b.component.size();
@@ -617,11 +646,20 @@ inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_ge
 	g.proj_max[0] = b.proj_range.max.x; g.proj_max[1] = b.proj_range.max.y;
 	g.resolution[0] = res.x; g.resolution[1] = res.y;
 	std::vector<op_blend_image> ims(n);
+	const op_views* views = hip_bundle_views(b, 0);
+	if (views && op_views_count(views) != n) { fprintf(stderr, "hip_blend_images: %d resident views for %d components\n", op_views_count(views), n); exit(1); }
 	for (int i = 0; i < n; ++i) {
 		auto& c = b.component[i];
 		c.imgptr->load();
 		ims[i].data = c.imgptr->img->ptr(); ims[i].h = c.imgptr->height(); ims[i].w = c.imgptr->width(); ims[i].on_device = 0;
 		ims[i].mat_h = c.imgptr->img->height(); ims[i].mat_w = c.imgptr->img->width();      // != h / w after a cylinder pre-warp (op_blend_image)
+		if (views) {    // the resident view stands for the Mat it was uploaded from; a Mat replaced since (cylinder pre-warp) keeps the host path
+			op_blend_image v;
+			PANO_HIP_CHECK(op_views_blend_image(views, i, &v));
+			if (v.h == ims[i].mat_h && v.w == ims[i].mat_w && ims[i].mat_h == ims[i].h && ims[i].mat_w == ims[i].w) {
+				ims[i].data = v.data; ims[i].on_device = v.on_device;
+			}
+		}
 		for (int k = 0; k < 9; ++k) ims[i].homo_inv[k] = c.homo_inv[k];
 		ims[i].range[0] = c.range.min.x; ims[i].range[1] = c.range.min.y; ims[i].range[2] = c.range.max.x; ims[i].range[3] = c.range.max.y;
 	}
@@ -883,6 +921,7 @@ class HipStitcher {
 
 		Mat32f build() {                                            // stitcher.cc:32-64
 			calc_feature();
+			bundle.views = resident_views ? feats.views : nullptr;
 			pairwise_matches.assign(imgs.size(), std::vector<MatchInfo>(imgs.size()));
 			if (config::ORDERED_INPUT) linear_pairwise_match();
 			else pairwise_match();
@@ -923,11 +962,15 @@ class HipStitcher {
 		bool vignetting = false;
 		std::array<float, 3> vignette_poly = {0.f, 0.f, 0.f};
 		std::vector<float> gains;
+		// resident views: calc_feature uploads the images once (bytes when they are exact k / 255, fp32 otherwise) and SIFT,
+		// the overlap passes and the blend all read that upload; off by default.  The panorama is the same bit for bit.
+		bool resident_views = false;
 
 		void calc_feature() {                                       // stitcherbase.cc:9-27
 			std::vector<const Mat32f*> ptrs;
 			for (auto& r : imgs) ptrs.push_back(r.img);
-			feats = HipSIFTDetector().calc_feature(ptrs);
+			bundle.views = nullptr;                                 // the previous upload is released by the assignment below
+			feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
 			keypoints.resize(imgs.size());
 			for (size_t k = 0; k < imgs.size(); ++k) {
 				keypoints[k].clear();

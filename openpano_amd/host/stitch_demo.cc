@@ -23,6 +23,8 @@
 // coefficients a1, a2, a3, where --gain-compensation puts its gains.
 // --png PATH (anywhere): additionally writes the panorama out.bin holds as an 8-bit RGB PNG, encoded on the device
 // (hip_write_png: write_rgb's quantisation, lib/imgio.cc:25-41); out.bin is the same with and without it.
+// --resident-views (anywhere): the images are uploaded once (HipStitcher::resident_views; bytes when every pixel is an exact
+// k / 255, fp32 otherwise) and SIFT, the overlap passes and the blend read that upload; out.bin is the same with and without it.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
@@ -83,11 +85,13 @@ static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::
 // Stitcher::build() under ESTIMATE_CAMERA (stitch/stitcher.cc:32-64), stage by stage so that every
 // intermediate can be written out
 static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby,
-		bool vig, const char* png_path) {
+		bool vig, const char* png_path, bool resident) {
 	Stitcher st(mats, base_seed);
+	st.resident_views = resident;
 	FILE* fo = fopen(out_path, "wb");
 	if (!fo) { perror(out_path); return 2; }
 	st.calc_feature();
+	st.bundle.views = resident ? st.feats.views : nullptr;     // what HipStitcher::build() does under resident_views
 	put_features(fo, st.feats);
 	const int n = (int)mats.size();
 	st.pairwise_matches.assign(n, std::vector<MatchInfo>(n));
@@ -134,8 +138,9 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 
 // Stitcher::build() as a client calls it, gain compensation per HipStitcher::gain_compensation
 static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain, int gbx, int gby, bool vig,
-		const char* png_path) {
+		const char* png_path, bool resident) {
 	Stitcher st(mats, base_seed);
+	st.resident_views = resident;
 	st.gain_compensation = gain;
 	st.vignetting = vig;
 	st.gain_blocks_x = gbx; st.gain_blocks_y = gby;
@@ -157,11 +162,13 @@ int main(int argc, char** argv) {
 	int gbx = 1, gby = 1;
 	bool vig = false;
 	const char* png_path = nullptr;
+	bool resident = false;
 	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
 			if (std::string(argv[k]) == "--gain-compensation") gain = true;
 			else if (std::string(argv[k]) == "--vignetting") vig = true;
+			else if (std::string(argv[k]) == "--resident-views") resident = true;
 			else if (std::string(argv[k]) == "--png" && k + 1 < argc) png_path = argv[++k];
 			else if (std::string(argv[k]) == "--gain-blocks" && k + 1 < argc) {
 				if (sscanf(argv[++k], "%dx%d", &gbx, &gby) != 2 || gbx < 1 || gbx > 16 || gby < 1 || gby > 16) {
@@ -174,7 +181,7 @@ int main(int argc, char** argv) {
 		argc = m;
 	}
 	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--resident-views]\n", argv[0]); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
@@ -191,8 +198,8 @@ int main(int argc, char** argv) {
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
-	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby, vig, png_path);
-	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path);
+	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby, vig, png_path, resident);
+	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
 
 	// ---- StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27)
 	std::vector<ImageRef> imgs;
@@ -200,7 +207,7 @@ int main(int argc, char** argv) {
 	SIFTDetector feature_det;
 	std::vector<const Mat32f*> ptrs;
 	for (auto& r : imgs) ptrs.push_back(r.img);
-	HipFeatureSet fs = feature_det.calc_feature(ptrs);
+	HipFeatureSet fs = feature_det.calc_feature(ptrs, resident);
 	FILE* fo = fopen(argv[2], "wb");
 	if (!fo) { perror(argv[2]); return 2; }
 	for (int k = 0; k < n; ++k) {
@@ -239,6 +246,7 @@ int main(int argc, char** argv) {
 	for (auto& r : infos) all = all && r.first;
 	if (all) {
 		ConnectedImages bundle;
+		bundle.views = fs.views;                                    // NULL without --resident-views
 		bundle.proj_method = ConnectedImages::flat;
 		bundle.identity_idx = n >> 1;                               // stitcher.cc:139
 		std::vector<Homography> to_mid(n, Homography::I());
