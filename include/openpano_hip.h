@@ -181,6 +181,10 @@ int op_debug_set_raw_capacity(op_ctx* ctx, int cap);
  * window samples (sift.cc:110-146) whose per-bin lists, padded to float4s, need more is sorted and accumulated in two
  * passes of 32 samples; exposed so that tests can force that path (0: always). */
 int op_debug_set_desc_list_cap(op_ctx* ctx, int floats);
+/* The process-wide device pool, read under its lock: blocks handed out and not yet returned, their bytes (size
+ * classes), and the bytes of returned blocks the pool keeps for reuse.  Any pointer may be NULL.  Exposed so that tests
+ * can check that every call gives back what it took, on refusals as well. */
+int op_debug_pool_stats(int64_t* live_blocks, int64_t* live_bytes, int64_t* cached_bytes);
 
 /* =====================================================================================
  * MATCH -- replaces PairWiseMatcher (feature/matcher.hh:40-67, matcher.cc:73-135) as used by

@@ -1091,8 +1091,6 @@ void cyl_proj(const CylProj& P, double px, double py, double out[2]) {       // 
 	out[1] = (py - P.cy) / (std::hypot(px - P.cx, (double)P.r));
 }
 
-struct Freer { std::vector<void*> v; ~Freer() { for (void* p : v) pool_free(p); } };
-
 // The transcendentals of the canvas -> space map, evaluated by the host libm exactly where the reference evaluates
 // them (stitcher_image.cc:144-145 + projection.hh:38-40,66-68): per column j  sin / cos of  j * resolution.x + min.x,
 // per row i  tan of  i * resolution.y + min.y  (spherical) or that value itself (cylindrical).  (w1, h1) = canvas + 1.
@@ -1220,14 +1218,14 @@ int op_blend_canvas_dims(const op_blend_geom* g, const op_blend_image* imgs, int
 }	// extern "C"
 
 namespace {
-// The op_blend_image array on the device as BlendImg (host images are uploaded; the uploads are freed with fr).  `who`
+// The op_blend_image array on the device as BlendImg (host images are uploaded; the uploads belong to own).  `who`
 // prefixes the error messages.
-int upload_images(op_ctx* ctx, const char* who, const op_blend_geom* g, const op_blend_image* imgs, int n, Freer& fr,
-		std::vector<BlendImg>& h_imgs, long long& roi_total, long long& max_roi, BlendImg** d_out) {
+int upload_images(op_ctx* ctx, const char* who, const op_blend_geom* g, const op_blend_image* imgs, int n, CallBlocks& own,
+		std::vector<BlendImg>& h_imgs, long long& roi_total, long long& max_roi, bool& any_u8, BlendImg** d_out) {
 	hipStream_t st = ctx->stream;
 	const std::string w = who;
 	h_imgs.assign(n, BlendImg{});
-	roi_total = 0; max_roi = 0;
+	roi_total = 0; max_roi = 0; any_u8 = false;      // any_u8: the set holds a byte view (the U8 kernel instances)
 	for (int k = 0; k < n; ++k)       // the flag word, before any device work
 		if (imgs[k].on_device & ~(OP_SRC_DEVICE | OP_SRC_U8)) OP_FAIL(OP_ERR_INVALID, w + ": unknown source flag on image " + std::to_string(k));
 	for (int k = 0; k < n; ++k) {
@@ -1237,12 +1235,12 @@ int upload_images(op_ctx* ctx, const char* who, const op_blend_geom* g, const op
 		b.h = s.h; b.w = s.w;
 		b.mh = s.mat_h > 0 ? s.mat_h : s.h; b.mw = s.mat_w > 0 ? s.mat_w : s.w;
 		if (b.mh < 2 || b.mw < 2) OP_FAIL(OP_ERR_INVALID, w + ": bad pixel buffer size of image " + std::to_string(k));
-		b.u8 = (s.on_device & OP_SRC_U8) ? 1 : 0;
+		b.u8 = (s.on_device & OP_SRC_U8) ? 1 : 0; any_u8 = any_u8 || b.u8;
 		if (s.on_device & OP_SRC_DEVICE) b.data = s.data;
 		else {            // a host view goes up in the type it has: 3 h w bytes, or 12 h w
 			const size_t bytes = (b.u8 ? 1 : sizeof(float)) * 3 * (size_t)b.mh * b.mw;
 			void* d = nullptr;
-			HIPCHK(pool_alloc(&d, bytes)); fr.v.push_back(d);
+			HIPCHK(own.alloc(&d, bytes));
 			HIPCHK(hipMemcpyAsync(d, s.data, bytes, hipMemcpyHostToDevice, st));
 			b.data = d;
 		}
@@ -1255,7 +1253,7 @@ int upload_images(op_ctx* ctx, const char* who, const op_blend_geom* g, const op
 		max_roi = std::max(max_roi, (long long)b.rw * b.rh);
 	}
 	BlendImg* d_imgs = nullptr;
-	HIPCHK(pool_alloc((void**)&d_imgs, sizeof(BlendImg) * n)); fr.v.push_back(d_imgs);
+	HIPCHK(own.alloc(&d_imgs, sizeof(BlendImg) * n));
 	HIPCHK(hipMemcpyAsync(d_imgs, h_imgs.data(), sizeof(BlendImg) * n, hipMemcpyHostToDevice, st));
 	*d_out = d_imgs;
 	return OP_OK;
@@ -1287,35 +1285,30 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 	rc = op_blend_canvas_dims(g, imgs, n, &H, &W);
 	if (rc != OP_OK) return rc;
 	if (H <= 0 || W <= 0) OP_FAIL(OP_ERR_INVALID, std::string(who) + ": empty canvas");
-	Freer fr;
+	CallBlocks own({ctx->stream});
 	std::vector<BlendImg> h_imgs;
-	long long roi_total = 0, max_roi = 0;
+	long long roi_total = 0, max_roi = 0; bool any_u8 = false;
 	BlendImg* d_imgs = nullptr;
-	rc = upload_images(ctx, who, g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
+	rc = upload_images(ctx, who, g, imgs, n, own, h_imgs, roi_total, max_roi, any_u8, &d_imgs);
 	if (rc != OP_OK) return rc;
 	float* d_gains = nullptr;
 	if (gm != GAIN_NONE) {       // the whole table, once per call
 		const size_t ng = gm == GAIN_VIGNETTE ? 3 * (size_t)n + 3 : 3 * (size_t)n * (gm == GAIN_BLOCK ? (size_t)gbx * gby : 1);
-		HIPCHK(pool_alloc((void**)&d_gains, sizeof(float) * ng)); fr.v.push_back(d_gains);
+		HIPCHK(own.alloc(&d_gains, sizeof(float) * ng));
 		HIPCHK(hipMemcpyAsync(d_gains, gains, sizeof(float) * ng, hipMemcpyHostToDevice, st));
 	}
-	op_canvas* cv = new op_canvas;
-	cv->h = H; cv->w = W; cv->device = ctx->device;
-	if (pool_alloc((void**)&cv->data, sizeof(float) * 3 * (size_t)H * W) != hipSuccess) { delete cv; OP_FAIL(OP_ERR_HIP, std::string(who) + ": canvas allocation failed"); }
+	float* canvas = nullptr;
+	if (own.alloc(&canvas, sizeof(float) * 3 * (size_t)H * W) != hipSuccess) OP_FAIL(OP_ERR_HIP, std::string(who) + ": canvas allocation failed");
 	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
 	const dim3 cgrid((W + 63) / 64, (H + 3) / 4);
 	BlendTrig trig{nullptr, nullptr, 0, 0};
 	if (bg.method != 0) {
 		HostScope hs(ctx, "blend trig tables (host)");
 		hipError_t e = trig_tables(ctx, bg, W + 1, H + 1, &trig);
-		if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string(who) + ": trig tables: " + hipGetErrorString(e)); }
+		if (e != hipSuccess) OP_FAIL(OP_ERR_HIP, std::string(who) + ": trig tables: " + hipGetErrorString(e));
 	}
-#define BCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-	pool_free(cv->data); delete cv; return OP_ERR_HIP; } } while (0)
 	// the instances of the gain mode (gbx / gby are read by GAIN_BLOCK only)
 	// and of the set's source types: the byte sampler is compiled into the U8 instances only, an all-fp32 call runs the others
-	bool any_u8 = false;
-	for (const BlendImg& b : h_imgs) any_u8 = any_u8 || b.u8;
 	auto linear = k_blend_linear<GAIN_NONE, false>; auto first = k_mb_first_fused<GAIN_NONE, false>;
 #define OP_GM_CASE(M) if (gm == M) { linear = any_u8 ? k_blend_linear<M, true> : k_blend_linear<M, false>; \
 	first = any_u8 ? k_mb_first_fused<M, true> : k_mb_first_fused<M, false>; }
@@ -1323,8 +1316,8 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 #undef OP_GM_CASE
 	if (cfg->MULTIBAND <= 0) {
 		ProfScope ps(ctx, "blend linear");
-		hipLaunchKernelGGL(linear, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, cv->data, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
-		BCHK(hipGetLastError());
+		hipLaunchKernelGGL(linear, cgrid, dim3(256), 0, st, bg, trig, d_imgs, n, canvas, H, W, cfg->ORDERED_INPUT, cfg->LAZY_READ, d_gains, gbx, gby);
+		HIPCHK(hipGetLastError());
 	} else {
 		const int L = cfg->MULTIBAND;
 		// every level's plane is kept when they fit comfortably (L x 16 bytes per ROI pixel: 0.2 GB per level for 38 views):
@@ -1334,14 +1327,14 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 		const int nplanes = keep_all ? L : 2;
 		std::vector<float4*> lv(nplanes, nullptr);
 		float4* tmp = nullptr; unsigned char *mask = nullptr, *tmask = nullptr;
-		for (int l = 0; l < nplanes; ++l) { BCHK(pool_alloc((void**)&lv[l], sizeof(float4) * roi_total)); fr.v.push_back(lv[l]); }
-		BCHK(pool_alloc((void**)&mask, roi_total)); fr.v.push_back(mask);
-		BCHK(pool_alloc((void**)&tmask, (size_t)H * W)); fr.v.push_back(tmask);
+		for (int l = 0; l < nplanes; ++l) { HIPCHK(own.alloc(&lv[l], sizeof(float4) * roi_total)); }
+		HIPCHK(own.alloc(&mask, roi_total));
+		HIPCHK(own.alloc(&tmask, (size_t)H * W));
 		const dim3 rgrid((unsigned)((max_roi + 255) / 256), n);
 		{ ProfScope ps(ctx, "multiband first level");
 		  const dim3 fgrid((W + 1 + 63) / 64, (H + 1 + 3) / 4);
-		  hipLaunchKernelGGL(first, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, cv->data, tmask, H, W, d_gains, gbx, gby);
-		  BCHK(hipGetLastError()); }
+		  hipLaunchKernelGGL(first, fgrid, dim3(256), 0, st, bg, trig, d_imgs, n, lv[0], mask, canvas, tmask, H, W, d_gains, gbx, gby);
+		  HIPCHK(hipGetLastError()); }
 		bool band0_done = false;                 // level 0's band written by the fused blur
 		for (int level = 0; level < L; ++level) {
 			const int is_last = (level == L - 1);
@@ -1357,21 +1350,21 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 					for (int k = 0; k < n; ++k)
 						items = std::max(items, (unsigned)(((h_imgs[k].rw + two - 1) / two) * ((h_imgs[k].rh + segr - 1) / segr)));
 					band_done = level == 0;
-					if (C == 6 && level == 0) hipLaunchKernelGGL((k_mb_blur_fused<6, true>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, cv->data, tmask, H, W);
-					else if (C == 6) hipLaunchKernelGGL((k_mb_blur_fused<6, false>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, cv->data, tmask, H, W);
-					else if (level == 0) hipLaunchKernelGGL((k_mb_blur_fused<9, true>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, cv->data, tmask, H, W);
-					else hipLaunchKernelGGL((k_mb_blur_fused<9, false>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, cv->data, tmask, H, W);
+					if (C == 6 && level == 0) hipLaunchKernelGGL((k_mb_blur_fused<6, true>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, canvas, tmask, H, W);
+					else if (C == 6) hipLaunchKernelGGL((k_mb_blur_fused<6, false>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, canvas, tmask, H, W);
+					else if (level == 0) hipLaunchKernelGGL((k_mb_blur_fused<9, true>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, canvas, tmask, H, W);
+					else hipLaunchKernelGGL((k_mb_blur_fused<9, false>), dim3(items, n), dim3(256), 0, st, d_imgs, taps, cur, nxt, canvas, tmask, H, W);
 				} else {
-					if (!tmp) { BCHK(pool_alloc((void**)&tmp, sizeof(float4) * roi_total)); fr.v.push_back(tmp); }
+					if (!tmp) { HIPCHK(own.alloc(&tmp, sizeof(float4) * roi_total)); }
 					hipLaunchKernelGGL((k_mb_blur<true, 0>), rgrid, dim3(256), 0, st, d_imgs, taps, cur, tmp);
 					hipLaunchKernelGGL((k_mb_blur<false, 0>), rgrid, dim3(256), 0, st, d_imgs, taps, tmp, nxt);
 				}
-				BCHK(hipGetLastError());
+				HIPCHK(hipGetLastError());
 			}
 			if (level == 0) band0_done = band_done;
 			if (!keep_all && !band_done) { ProfScope ps(ctx, "multiband band");
-			  hipLaunchKernelGGL(k_mb_accumulate, cgrid, dim3(256), 0, st, d_imgs, n, cur, nxt, mask, cv->data, tmask, H, W, is_last);
-			  BCHK(hipGetLastError()); }
+			  hipLaunchKernelGGL(k_mb_accumulate, cgrid, dim3(256), 0, st, d_imgs, n, cur, nxt, mask, canvas, tmask, H, W, is_last);
+			  HIPCHK(hipGetLastError()); }
 		}
 		if (keep_all) {
 			ProfScope ps(ctx, "multiband band");
@@ -1379,18 +1372,17 @@ int blend_impl(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, const 
 			BandPlanes P; memset(&P, 0, sizeof(P));
 			for (int l = 0; l < NL; ++l) P.lv[l] = lv[first + l];
 			switch (NL) {
-#define OP_MB_CASE(N) case N: hipLaunchKernelGGL((k_mb_bands<N>), cgrid, dim3(256), 0, st, d_imgs, n, P, mask, cv->data, tmask, H, W); break;
+#define OP_MB_CASE(N) case N: hipLaunchKernelGGL((k_mb_bands<N>), cgrid, dim3(256), 0, st, d_imgs, n, P, mask, canvas, tmask, H, W); break;
 				OP_MB_CASE(1) OP_MB_CASE(2) OP_MB_CASE(3) OP_MB_CASE(4) OP_MB_CASE(5) OP_MB_CASE(6)
 #undef OP_MB_CASE
 				default: break;
 			}
-			BCHK(hipGetLastError());
+			HIPCHK(hipGetLastError());
 		}
 	}
-	BCHK(hipStreamSynchronize(st));
-#undef BCHK
+	HIPCHK(own.finish());
 	resolve_profile(ctx);
-	*out = cv;
+	*out = new op_canvas{own.release(canvas), H, W, ctx->device};      // born owning its block, on the last line
 	return OP_OK;
 }
 
@@ -1446,15 +1438,15 @@ int overlap_stats(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, con
 	const int hs_ = (H + stride - 1) / stride, ws_ = (W + stride - 1) / stride;
 	if (cap_lattice && (long long)hs_ * ws_ > VIG_MAX_LATTICE)
 		OP_FAIL(OP_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string((long long)hs_ * ws_) + " lattice points exceed 2^30 (raise the stride)");
-	Freer fr;
+	CallBlocks own({ctx->stream});
 	std::vector<BlendImg> h_imgs;
-	long long roi_total = 0, max_roi = 0;
+	long long roi_total = 0, max_roi = 0; bool any_u8 = false;
 	BlendImg* d_imgs = nullptr;
-	rc = upload_images(ctx, who, g, imgs, n, fr, h_imgs, roi_total, max_roi, &d_imgs);
+	rc = upload_images(ctx, who, g, imgs, n, own, h_imgs, roi_total, max_roi, any_u8, &d_imgs);
 	if (rc != OP_OK) return rc;
 	unsigned long long* d_stats = nullptr;         // entries counts, then entries x per values
 	const size_t stat_bytes = sizeof(unsigned long long) * (1 + per) * (size_t)entries;
-	HIPCHK(pool_alloc((void**)&d_stats, stat_bytes)); fr.v.push_back(d_stats);
+	HIPCHK(own.alloc(&d_stats, stat_bytes));
 	HIPCHK(hipMemsetAsync(d_stats, 0, stat_bytes, st));
 	const BlendGeom bg{g->proj_method, g->proj_min[0], g->proj_min[1], g->resolution[0], g->resolution[1]};
 	BlendTrig trig{nullptr, nullptr, 0, 0};
@@ -1462,15 +1454,13 @@ int overlap_stats(op_ctx* ctx, const op_config* cfg, const op_blend_geom* g, con
 		HostScope hs(ctx, "blend trig tables (host)");
 		HIPCHK(trig_tables(ctx, bg, W + 1, H + 1, &trig));
 	}
-	bool any_u8 = false;
-	for (const BlendImg& b : h_imgs) any_u8 = any_u8 || b.u8;
 	{ ProfScope ps(ctx, label);
 	  hipLaunchKernelGGL(any_u8 ? kernel_u8 : kernel, dim3((ws_ + 63) / 64, (hs_ + 3) / 4), dim3(256), sizeof(unsigned long long) * ((n + 63) / 64), st,
 	                     bg, trig, d_imgs, n, H, W, stride, cfg->LAZY_READ, extra..., d_stats, d_stats + entries);
 	  HIPCHK(hipGetLastError()); }
 	HIPCHK(hipMemcpyAsync(count, d_stats, sizeof(int64_t) * (size_t)entries, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(values, d_stats + entries, sizeof(int64_t) * per * (size_t)entries, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
+	HIPCHK(own.finish());
 	resolve_profile(ctx);
 	return OP_OK;
 }
@@ -1850,11 +1840,11 @@ int op_canvas_crop(op_ctx* ctx, const op_canvas* c, op_canvas** out, int* x0, in
 	hipStream_t st = ctx->stream;
 	const int h = c->h, w = c->w;
 	if ((size_t)(w + (w + CROP_CHUNK - 1) / CROP_CHUNK) * sizeof(int) > 150 * 1024) OP_FAIL(OP_ERR_UNSUPPORTED, "op_canvas_crop: canvas wider than 38000 px");
-	Freer fr;
+	CallBlocks own({ctx->stream});
 	int* d_height = nullptr; int4* d_best = nullptr; int* d_rect = nullptr;
-	HIPCHK(pool_alloc((void**)&d_height, sizeof(int) * (size_t)h * w)); fr.v.push_back(d_height);
-	HIPCHK(pool_alloc((void**)&d_best, sizeof(int4) * h)); fr.v.push_back(d_best);
-	HIPCHK(pool_alloc((void**)&d_rect, sizeof(int) * 4)); fr.v.push_back(d_rect);
+	HIPCHK(own.alloc(&d_height, sizeof(int) * (size_t)h * w));
+	HIPCHK(own.alloc(&d_best, sizeof(int4) * h));
+	HIPCHK(own.alloc(&d_rect, sizeof(int) * 4));
 	HIPCHK(hipFuncSetAttribute((const void*)k_crop_lines, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));   // idempotent
 	int rect[4];
 	{ ProfScope ps(ctx, "crop");
@@ -1867,20 +1857,19 @@ int op_canvas_crop(op_ctx* ctx, const op_canvas* c, op_canvas** out, int* x0, in
 	  HIPCHK(hipGetLastError()); }
 	HIPCHK(hipMemcpyAsync(rect, d_rect, sizeof(rect), hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
-	op_canvas* cv = new op_canvas;
-	cv->h = rect[3]; cv->w = rect[2]; cv->device = ctx->device;
-	const size_t n = (size_t)cv->h * cv->w * 3;
-	if (pool_alloc((void**)&cv->data, sizeof(float) * (n ? n : 1)) != hipSuccess) { delete cv; OP_FAIL(OP_ERR_HIP, "op_canvas_crop: allocation failed"); }
+	const size_t n = (size_t)rect[3] * rect[2] * 3;
+	float* data = nullptr;
+	if (own.alloc(&data, sizeof(float) * (n ? n : 1)) != hipSuccess) OP_FAIL(OP_ERR_HIP, "op_canvas_crop: allocation failed");
 	if (n) {
-		hipLaunchKernelGGL(k_crop_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->data, w, rect[0], rect[1], cv->data, cv->h, cv->w);
-		hipError_t e = hipGetLastError();
-		if (e == hipSuccess) e = hipStreamSynchronize(st);
-		if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string("op_canvas_crop: ") + hipGetErrorString(e)); }
+		hipLaunchKernelGGL(k_crop_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->data, w, rect[0], rect[1], data, rect[3], rect[2]);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipStreamSynchronize(st));
 	}
+	own.settled();
 	resolve_profile(ctx);
 	if (x0) *x0 = rect[0];
 	if (y0) *y0 = rect[1];
-	*out = cv;
+	*out = new op_canvas{own.release(data), rect[3], rect[2], ctx->device};      // born owning its block, on the last line
 	return OP_OK;
 }
 
@@ -1889,13 +1878,13 @@ int op_canvas_copy_u8(op_ctx* ctx, const op_canvas* c, unsigned char* host) {
 	HIPCHK(hipSetDevice(ctx->device));
 	const long long n = (long long)c->h * c->w * 3;
 	if (n == 0) return OP_OK;
-	Freer fr;
+	CallBlocks own({ctx->stream});
 	unsigned char* d = nullptr;
-	HIPCHK(pool_alloc((void**)&d, (size_t)n)); fr.v.push_back(d);
+	HIPCHK(own.alloc(&d, (size_t)n));
 	hipLaunchKernelGGL(k_to_u8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, c->data, n, d);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(host, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
+	HIPCHK(own.finish());
 	return OP_OK;
 }
 
@@ -1938,33 +1927,31 @@ int op_cyl_warp(op_ctx* ctx, const op_config* cfg, const op_image* img, double h
 	int rc = op_cyl_warp_shape(cfg, img->w, img->h, h_factor, nullptr, 0, &nw, &nh, off);
 	if (rc != OP_OK) return rc;
 	if (nw <= 0 || nh <= 0) OP_FAIL(OP_ERR_INVALID, "op_cyl_warp: empty output");
-	Freer fr;
+	CallBlocks own({ctx->stream});
 	if (img->dtype != OP_F32 && img->dtype != OP_U8) OP_FAIL(OP_ERR_INVALID, "op_cyl_warp: unknown dtype");
 	const bool u8 = img->dtype == OP_U8;
 	const void* src = img->data;
 	if (!img->on_device) {
 		const size_t bytes = (u8 ? 1 : sizeof(float)) * 3 * (size_t)img->h * img->w;
 		void* d = nullptr;
-		HIPCHK(pool_alloc(&d, bytes)); fr.v.push_back(d);
+		HIPCHK(own.alloc(&d, bytes));
 		HIPCHK(hipMemcpyAsync(d, img->data, bytes, hipMemcpyHostToDevice, st));
 		src = d;
 	}
 	const CylProj P = cyl_projector(img->w, img->h, h_factor, cfg->FOCAL_LENGTH);
-	op_canvas* cv = new op_canvas;
-	cv->h = nh; cv->w = nw; cv->device = ctx->device;
-	if (pool_alloc((void**)&cv->data, sizeof(float) * 3 * (size_t)nh * nw) != hipSuccess) { delete cv; OP_FAIL(OP_ERR_HIP, "op_cyl_warp: allocation failed"); }
+	float* data = nullptr;
+	if (own.alloc(&data, sizeof(float) * 3 * (size_t)nh * nw) != hipSuccess) OP_FAIL(OP_ERR_HIP, "op_cyl_warp: allocation failed");
 	const CylParams cp{P.cx, P.cy, off[0], off[1], 1.0 / P.sizefactor, P.r};
 	const double2* coltc = nullptr;
 	{ hipError_t e = cyl_tables(ctx, cp.offx, cp.sizefactor_inv, nw, &coltc);
-	  if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string("op_cyl_warp: trig table: ") + hipGetErrorString(e)); } }
+	  if (e != hipSuccess) OP_FAIL(OP_ERR_HIP, std::string("op_cyl_warp: trig table: ") + hipGetErrorString(e)); }
 	{ ProfScope ps(ctx, "cylinder warp");
-	  if (u8) hipLaunchKernelGGL(k_cyl_project<unsigned char>, dim3((nw + 63) / 64, (nh + 3) / 4), dim3(256), 0, st, cp, coltc, (const unsigned char*)src, img->h, img->w, cv->data, nh, nw);
-	  else hipLaunchKernelGGL(k_cyl_project<float>, dim3((nw + 63) / 64, (nh + 3) / 4), dim3(256), 0, st, cp, coltc, (const float*)src, img->h, img->w, cv->data, nh, nw); }
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e != hipSuccess) { pool_free(cv->data); delete cv; OP_FAIL(OP_ERR_HIP, std::string("op_cyl_warp: ") + hipGetErrorString(e)); }
+	  if (u8) hipLaunchKernelGGL(k_cyl_project<unsigned char>, dim3((nw + 63) / 64, (nh + 3) / 4), dim3(256), 0, st, cp, coltc, (const unsigned char*)src, img->h, img->w, data, nh, nw);
+	  else hipLaunchKernelGGL(k_cyl_project<float>, dim3((nw + 63) / 64, (nh + 3) / 4), dim3(256), 0, st, cp, coltc, (const float*)src, img->h, img->w, data, nh, nw); }
+	HIPCHK(hipGetLastError());
+	HIPCHK(own.finish());
 	resolve_profile(ctx);
-	*out = cv;
+	*out = new op_canvas{own.release(data), nh, nw, ctx->device};      // born owning its block, on the last line
 	return OP_OK;
 }
 
@@ -1986,8 +1973,9 @@ int op_views_upload(op_ctx* ctx, const op_image* imgs, int n, op_views** out) {
 		bytes[i] = (imgs[i].dtype == OP_U8 ? 1 : sizeof(float)) * 3 * (size_t)imgs[i].h * imgs[i].w;
 		off[i] = total; total += (bytes[i] + 255) & ~(size_t)255;
 	}
+	CallBlocks own({st});
 	char* block = nullptr;
-	HIPCHK(pool_alloc((void**)&block, total));
+	HIPCHK(own.alloc(&block, total));
 	// host images of one size at one constant stride (a contiguous array of frames, a decoder pool) go up in ONE copy
 	bool packed = n > 1;
 	for (int i = 0; i < n && packed; ++i) packed = !imgs[i].on_device && bytes[i] == bytes[0];
@@ -1998,10 +1986,10 @@ int op_views_upload(op_ctx* ctx, const op_image* imgs, int n, op_views** out) {
 	if (packed) e = hipMemcpy2DAsync(block, off[1], imgs[0].data, (size_t)hstride, bytes[0], (size_t)n, hipMemcpyHostToDevice, st);
 	else for (int i = 0; i < n && e == hipSuccess; ++i)
 		e = hipMemcpyAsync(block + off[i], imgs[i].data, bytes[i], imgs[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);       // the caller's host buffers are free again when this returns
-	if (e != hipSuccess) { pool_free(block); OP_FAIL(OP_ERR_HIP, std::string("op_views_upload: ") + hipGetErrorString(e)); }
+	if (e == hipSuccess) e = own.finish();       // the caller's host buffers are free again when this returns
+	if (e != hipSuccess) OP_FAIL(OP_ERR_HIP, std::string("op_views_upload: ") + hipGetErrorString(e));
 	op_views* v = new op_views;
-	v->ctx = ctx; v->block = block;
+	v->ctx = ctx; v->block = own.release(block);
 	v->imgs.resize(n);
 	for (int i = 0; i < n; ++i) v->imgs[i] = op_image{block + off[i], imgs[i].h, imgs[i].w, 1, imgs[i].dtype};
 	*out = v;

@@ -210,6 +210,15 @@ int op_ctx_sync(op_ctx* c) {
 	return OP_OK;
 }
 
+int op_debug_pool_stats(int64_t* live_blocks, int64_t* live_bytes, int64_t* cached_bytes) {
+	PoolState& P = pool();
+	std::lock_guard<std::mutex> lk(P.mu);
+	if (live_blocks) *live_blocks = (int64_t)P.live.size();
+	if (live_bytes) { *live_bytes = 0; for (auto& kv : P.live) *live_bytes += (int64_t)kv.second.second; }
+	if (cached_bytes) *cached_bytes = (int64_t)P.cached_bytes;
+	return OP_OK;
+}
+
 int op_debug_math(op_ctx* c, int which, const float* x, const float* y, int n, float* out) {
 	if (!c || !x || !out || n < 0 || which < 0 || which > 4) OP_FAIL(OP_ERR_INVALID, "op_debug_math: bad argument");
 	if (n == 0) return OP_OK;

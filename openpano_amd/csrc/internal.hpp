@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 #include "openpano_hip.h"
@@ -16,6 +18,21 @@ void op_ctx_release_workspace(op_ctx* c);
 #define OP_FAIL(code, msg) do { op_set_error(msg); return (code); } while (0)
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return OP_ERR_HIP; } } while (0)
+
+// grow-only device scratch (hipMalloc, not the pool): the arenas of a context and the SIFT workspace
+struct DevScratch {
+	void* p = nullptr; size_t cap = 0;
+	hipError_t ensure(size_t bytes) {
+		if (bytes <= cap) return hipSuccess;
+		if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }   // hipFree waits for the device
+		const size_t want = bytes + bytes / 8;
+		hipError_t e = hipMalloc(&p, want);
+		if (e != hipSuccess) return e;
+		cap = want;
+		return hipSuccess;
+	}
+	void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
 
 // per-stage device timing (HIP events on the context's stream), the counterpart of the
 // reference's TotalTimer table (lib/timer.hh:63-83); labels reuse the reference's where one exists
@@ -36,19 +53,6 @@ struct op_ctx {
 	// grow-only device scratch of the matcher and of RANSAC: a call's temporaries live here, so kernels that are
 	// still queued when the call returns (the per-pair sort into the result buffer) keep valid inputs -- the next
 	// call on this context is ordered behind them on the same stream (contexts are thread-compatible)
-	struct DevScratch {
-		void* p = nullptr; size_t cap = 0;
-		hipError_t ensure(size_t bytes) {
-			if (bytes <= cap) return hipSuccess;
-			if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }   // hipFree waits for the device
-			const size_t want = bytes + bytes / 8;
-			hipError_t e = hipMalloc(&p, want);
-			if (e != hipSuccess) return e;
-			cap = want;
-			return hipSuccess;
-		}
-		void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-	};
 	DevScratch match_arena, ransac_arena;
 	// blend: the canvas -> space map's transcendentals, tabulated per canvas column / row by the HOST libm (blend.hip,
 	// trig_tables): kept across calls with the same canvas geometry
@@ -112,6 +116,35 @@ void host_parallel_for(int n, const std::function<void(int)>& body, int grain = 
 hipError_t pool_alloc(void** p, size_t bytes);
 void pool_free(void* p);
 void pool_trim();     // release every cached block back to the runtime
+
+// The pool does not track streams, so a block may go back to it only when the stream that last touched it is idle.
+// CallBlocks is the one owner of the blocks (and events) a C-layer call allocates: made from the stream(s) the call works
+// on, it frees what it still holds on every exit and waits for its streams first, unless the call's own last wait was
+// finish() -- or settled() tells it of one.  A block that moves into a result handle is release()d on the call's last lines.
+struct CallBlocks {
+	std::vector<hipStream_t> streams; std::vector<void*> blocks; std::vector<hipEvent_t> events; bool idle = false;
+	explicit CallBlocks(std::vector<hipStream_t> s): streams(std::move(s)) {}
+	CallBlocks(const CallBlocks&) = delete; CallBlocks& operator=(const CallBlocks&) = delete;
+	template <typename T> hipError_t alloc(T** p, size_t bytes) { hipError_t e = pool_alloc((void**)p, bytes); if (e == hipSuccess) blocks.push_back((void*)*p); return e; }
+	hipError_t event() { hipEvent_t ev; hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming); if (e == hipSuccess) events.push_back(ev); return e; }      // events.back()
+	// the caller (a result handle) owns p from here on
+	template <typename T> T* release(T* p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), (void*)p), blocks.end()); return p; }
+	template <typename T> void free(T*& p) { pool_free(release(p)); p = nullptr; }      // at once: only behind a wait
+	hipError_t finish() {                          // the call's last wait: hipStreamSynchronize of every stream, the first error returned
+		hipError_t r = hipSuccess;
+		for (hipStream_t s : streams) { hipError_t e = hipStreamSynchronize(s); if (r == hipSuccess) r = e; }
+		idle = true;                               // a failed wait cannot be helped: the blocks are freed regardless
+		return r;
+	}
+	void settled() { idle = true; }
+	~CallBlocks() {
+		if (!idle && !(blocks.empty() && events.empty())) (void)finish();
+		for (void* b : blocks) pool_free(b);
+		for (hipEvent_t e : events) hipEventDestroy(e);
+	}
+};
+// waits for a forked stream when its scope ends between the fork (armed) and the join (disarmed)
+struct StreamJoin { hipStream_t stream = nullptr; bool armed = false; ~StreamJoin() { if (armed) (void)hipStreamSynchronize(stream); } };
 
 // ---------------------------------------------------------------------------------------
 // HBM layout of one image's scale space ("image workspace", ws_stride floats per image):

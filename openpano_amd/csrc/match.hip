@@ -16,7 +16,6 @@
 #include "internal.hpp"
 #include <cfloat>
 #include <cstring>
-#include <memory>
 #include <algorithm>
 #include <mutex>
 
@@ -52,6 +51,7 @@ struct op_matches {
 	}
 };
 
+using MatchesPtr = std::unique_ptr<op_matches, void (*)(op_matches*)>;      // a result handle is owned from birth
 int op_matches_num_pairs(const op_matches* m) { return m->npairs; }
 const std::vector<int>& op_matches_counts(const op_matches* m) { return m->count; }
 const std::vector<int64_t>& op_matches_offsets(const op_matches* m) { return m->offset; }
@@ -725,10 +725,10 @@ int op_match_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, cons
 	hipStream_t st = ctx->stream;
 	const long long total = fv.offsets[fv.n];
 	if (!fv.desc) OP_FAIL(OP_ERR_INVALID, "op_match_pairs: features hold coordinates only (built without descriptors)");
-	op_matches* m = new op_matches;
+	MatchesPtr m(new op_matches, op_matches_free);
 	m->npairs = npairs; m->count.assign(npairs, 0); m->offset.assign(npairs + 1, 0); m->lim.assign((size_t)npairs * 2, 0);
 	m->device = ctx->device; m->stream = ctx->stream;
-	if (npairs == 0 || total == 0) { m->host_valid = true; m->h_idx.resize(2); *out = m; return OP_OK; }
+	if (npairs == 0 || total == 0) { m->host_valid = true; m->h_idx.resize(2); *out = m.release(); return OP_OK; }
 
 	std::unique_ptr<HostScope> hs(new HostScope(ctx, "matcher work list + launches (host)"));
 	std::vector<WorkItem> work;
@@ -737,7 +737,7 @@ int op_match_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, cons
 	size_t n_items = 0;                                                  // row blocks of all pairs = workgroups of a sweep
 	for (int p = 0; p < npairs; ++p) {
 		const int i = pairs[2 * p], j = pairs[2 * p + 1];
-		if (i < 0 || j < 0 || i >= fv.n || j >= fv.n) { delete m; OP_FAIL(OP_ERR_INVALID, "op_match_pairs: image index out of range"); }
+		if (i < 0 || j < 0 || i >= fv.n || j >= fv.n) OP_FAIL(OP_ERR_INVALID, "op_match_pairs: image index out of range");
 		const int rev = fv.counts[i] > fv.counts[j];                       // matcher.cc:21: the smaller set queries
 		const int ia = rev ? j : i, ib = rev ? i : j;
 		PairDesc& pd = pds[p];
@@ -771,9 +771,9 @@ int op_match_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, cons
 				for (int c = 0; c < 8; ++c) if (k < chunk[c].size()) work.push_back(chunk[c][k]);
 		}
 	};
-	if (res_rows >= (1LL << 30)) { delete m; OP_FAIL(OP_ERR_CAPACITY, "op_match_pairs: too many rows in one call; split the pair list"); }
+	if (res_rows >= (1LL << 30)) OP_FAIL(OP_ERR_CAPACITY, "op_match_pairs: too many rows in one call; split the pair list");
 	for (int i = 0; i < fv.n; ++i)
-		if (fv.counts[i] >= (1 << 22)) { delete m; OP_FAIL(OP_ERR_CAPACITY, "op_match_pairs: an image with 4 M descriptors or more (the sweep addresses a descriptor set with 32-bit byte offsets)"); }
+		if (fv.counts[i] >= (1 << 22)) OP_FAIL(OP_ERR_CAPACITY, "op_match_pairs: an image with 4 M descriptors or more (the sweep addresses a descriptor set with 32-bit byte offsets)");
 	const size_t nres = (size_t)std::max<long long>(res_rows, 1);
 	const int slow_cap = (int)std::min<long long>(std::max<long long>(res_rows, 1), 1 << 22);
 
@@ -799,18 +799,16 @@ int op_match_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, cons
 	char* arena = nullptr;
 	const size_t hres_bytes = al(sizeof(int) * (3 + (size_t)npairs));
 	char* pin = (char*)ctx->pinned_scratch(hres_bytes + al(up_bytes));          // pinned: copies run at link rate, asynchronously
-	int rc = OP_OK;
-	if (!pin) { delete m; OP_FAIL(OP_ERR_HIP, "op_match_pairs: pinned host allocation failed"); }
+	if (!pin) OP_FAIL(OP_ERR_HIP, "op_match_pairs: pinned host allocation failed");
 	int* h_res = (int*)pin;                                                // slow_fwd_n, slow_rev_n, match count, matches per pair
 	h_res[0] = h_res[1] = h_res[2] = 0;
 	std::memcpy(pin + hres_bytes, pds.data(), sizeof(PairDesc) * npairs);
-#define MCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); rc = OP_ERR_HIP; goto done; } } while (0)
-	MCHK(ctx->match_arena.ensure(arena_bytes));
+	HIPCHK(ctx->match_arena.ensure(arena_bytes));
 	arena = (char*)ctx->match_arena.p;
 	{
 		int* ctrl = (int*)(arena + o_ctrl);
 		int* d_pcnt = ctrl + 4; int* d_fill = ctrl + 4 + 2 * (size_t)npairs; int* d_poff = ctrl + 4 + 3 * (size_t)npairs;
-		MCHK(hipMemsetAsync(ctrl, 0, sizeof(int) * n_ctrl, st));
+		HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(int) * n_ctrl, st));
 		MatchState S;
 		S.desc = fv.desc; S.split = (const uint4*)(arena + o_split); S.norms = (const float*)(arena + o_norms);
 		S.gmax_bits = (const unsigned*)ctrl; S.pairs = (const PairDesc*)(arena + o_up);
@@ -825,81 +823,79 @@ int op_match_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, cons
 			ProfScope ps(ctx, "matcher norms");
 			hipLaunchKernelGGL(k_split_bf16, dim3((unsigned)std::min<long long>((total * 16 + 255) / 256, 1024)), dim3(256), 0, st, fv.desc, total,
 					(uint4*)(arena + o_split), (float*)(arena + o_norms), (unsigned*)ctrl);
-			MCHK(hipGetLastError());
+			HIPCHK(hipGetLastError());
 		}
 		// the split kernel is on its way: the work list (a sort and a deal of the pairs) is built while it runs
 		build_work_list();
-		if (work.size() != n_items) { op_set_error("op_match_pairs: work list size mismatch"); rc = OP_ERR_HIP; goto done; }
+		if (work.size() != n_items) OP_FAIL(OP_ERR_HIP, "op_match_pairs: work list size mismatch");
 		if (!work.empty()) std::memcpy(pin + hres_bytes + sizeof(PairDesc) * npairs, work.data(), sizeof(WorkItem) * work.size());
-		MCHK(hipMemcpyAsync(arena + o_up, pin + hres_bytes, up_bytes, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(arena + o_up, pin + hres_bytes, up_bytes, hipMemcpyHostToDevice, st));
 		if (!work.empty()) {
 			{
 				ProfScope ps(ctx, "matcher mfma forward");
 				hipLaunchKernelGGL(k_match_sweep<false>, dim3((unsigned)work.size()), dim3(256), 0, st, S, d_work);
-				MCHK(hipGetLastError());
+				HIPCHK(hipGetLastError());
 				if (grouped) hipLaunchKernelGGL(k_slow_order<false>, dim3(1), dim3(1024), 0, st, S, fv.n);
 				hipLaunchKernelGGL(k_match_slow<false>, dim3(slow_grid(ctx->match_slow_seen[0])), dim3(256), 0, st, S, grouped);
-				MCHK(hipGetLastError());
+				HIPCHK(hipGetLastError());
 			}
 			{
 				// the reverse strip: same work list; row blocks beyond a pair's survivor count exit at once
 				ProfScope ps(ctx, "matcher mfma reverse");
 				hipLaunchKernelGGL(k_match_sweep<true>, dim3((unsigned)work.size()), dim3(256), 0, st, S, d_work);
-				MCHK(hipGetLastError());
+				HIPCHK(hipGetLastError());
 				if (grouped) hipLaunchKernelGGL(k_slow_order<true>, dim3(1), dim3(1024), 0, st, S, fv.n);
 				hipLaunchKernelGGL(k_match_slow<true>, dim3(slow_grid(ctx->match_slow_seen[1])), dim3(256), 0, st, S, grouped);
-				MCHK(hipGetLastError());
+				HIPCHK(hipGetLastError());
 			}
 			{
 				ProfScope ps(ctx, "matcher result lists");
 				hipLaunchKernelGGL(k_match_offsets, dim3(1), dim3(1024), 0, st, (const int*)d_pcnt, npairs, d_poff);
 				hipLaunchKernelGGL(k_match_place, dim3((unsigned)std::min<size_t>((nres + 255) / 256, 512)), dim3(256), 0, st, S, (const int*)d_poff, d_fill, (int2*)(arena + o_seg));
-				MCHK(hipGetLastError());
+				HIPCHK(hipGetLastError());
 			}
-			MCHK(hipMemcpyAsync(h_res, ctrl + 1, sizeof(int) * (3 + (size_t)npairs), hipMemcpyDeviceToHost, st));
+			HIPCHK(hipMemcpyAsync(h_res, ctrl + 1, sizeof(int) * (3 + (size_t)npairs), hipMemcpyDeviceToHost, st));
 		}
 		hs.reset(); hs.reset(new HostScope(ctx, "matcher wait + counts (host)"));
-		MCHK(hipStreamSynchronize(st));
+		HIPCHK(hipStreamSynchronize(st));
 		resolve_profile(ctx);                            // (the sort below stays pending until the next resolve: no second wait)
 		if (!work.empty()) {
 			ctx->match_slow_seen[0] = h_res[0]; ctx->match_slow_seen[1] = h_res[1];
 			if (h_res[0] > slow_cap || h_res[1] > slow_cap) {
 				// more rows needed the exact full scan than the queue holds (> 4 M rows of near-duplicate
 				// descriptors in one call): the rows beyond the queue were not matched -- never return that as OP_OK
-				op_set_error("op_match_pairs: exact-scan queue overflow (" + std::to_string(std::max(h_res[0], h_res[1])) + " rows > " +
+				OP_FAIL(OP_ERR_CAPACITY, "op_match_pairs: exact-scan queue overflow (" + std::to_string(std::max(h_res[0], h_res[1])) + " rows > " +
 						std::to_string(slow_cap) + "); split the pair list");
-				rc = OP_ERR_CAPACITY; goto done;
 			}
 			for (int p = 0; p < npairs; ++p) { m->count[p] = h_res[3 + p]; m->offset[p + 1] = m->offset[p] + h_res[3 + p]; }
 			m->total = m->offset[npairs];
-			if (m->total != h_res[2]) { op_set_error("op_match_pairs: per-pair counts do not add up to the match count"); rc = OP_ERR_HIP; goto done; }
+			if (m->total != h_res[2]) OP_FAIL(OP_ERR_HIP, "op_match_pairs: per-pair counts do not add up to the match count");
 			if (m->total) {
 				// the sorted lists go straight into the result buffer (exact size, known now); the kernel reads the
 				// context's arena, which stays valid: whatever uses this context next is ordered behind it
-				MCHK(pool_alloc((void**)&m->d_idx, sizeof(int) * 2 * (size_t)m->total));
+				CallBlocks own({st});                      // until `produced` guards the block: a failure in between waits for the sort
+				int* d_idx = nullptr;
+				HIPCHK(own.alloc(&d_idx, sizeof(int) * 2 * (size_t)m->total));
 				ProfScope ps(ctx, "matcher result lists");
-				hipLaunchKernelGGL(k_match_sort, dim3((unsigned)npairs), dim3(256), 0, st, (const int*)d_pcnt, (const int*)d_poff, (const int2*)(arena + o_seg), (int2*)m->d_idx);
-				MCHK(hipGetLastError());
-				MCHK(hipEventCreateWithFlags(&m->produced, hipEventDisableTiming));
-				MCHK(hipEventRecord(m->produced, st));
+				hipLaunchKernelGGL(k_match_sort, dim3((unsigned)npairs), dim3(256), 0, st, (const int*)d_pcnt, (const int*)d_poff, (const int2*)(arena + o_seg), (int2*)d_idx);
+				HIPCHK(hipGetLastError());
+				HIPCHK(hipEventCreateWithFlags(&m->produced, hipEventDisableTiming));
+				HIPCHK(hipEventRecord(m->produced, st));
+				m->d_idx = own.release(d_idx);
 			}
 		}
 	}
-done:
-	hs.reset();
-#undef MCHK
-	if (rc != OP_OK) { delete m; return rc; }
-	*out = m;
+	*out = m.release();
 	return OP_OK;
 }
 
 
 int op_matches_from_host(const int* const* idx_pairs, const int* counts, int npairs, op_matches** out) {
 	if (!idx_pairs || !counts || npairs < 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_matches_from_host: bad argument");
-	op_matches* m = new op_matches;
+	MatchesPtr m(new op_matches, op_matches_free);
 	m->npairs = npairs; m->count.assign(npairs, 0); m->offset.assign(npairs + 1, 0);
 	for (int p = 0; p < npairs; ++p) {
-		if (counts[p] < 0) { delete m; OP_FAIL(OP_ERR_INVALID, "negative count"); }
+		if (counts[p] < 0) OP_FAIL(OP_ERR_INVALID, "negative count");
 		m->count[p] = counts[p]; m->offset[p + 1] = m->offset[p] + counts[p];
 	}
 	m->total = m->offset[npairs];
@@ -907,7 +903,7 @@ int op_matches_from_host(const int* const* idx_pairs, const int* counts, int npa
 	for (int p = 0; p < npairs; ++p)
 		if (counts[p]) std::memcpy(m->h_idx.data() + 2 * m->offset[p], idx_pairs[p], sizeof(int) * 2 * (size_t)counts[p]);
 	m->host_valid = true;
-	*out = m;
+	*out = m.release();
 	return OP_OK;
 }
 
@@ -920,7 +916,7 @@ int op_matches_concat(op_ctx* ctx, const op_matches* a, const op_matches* b, op_
 	if (!ctx || !a || !b || !out) OP_FAIL(OP_ERR_INVALID, "op_matches_concat: bad argument");
 	if (!a->parts.empty() || !b->parts.empty()) OP_FAIL(OP_ERR_UNSUPPORTED, "op_matches_concat: results of a device group cannot be joined");
 	HIPCHK(hipSetDevice(ctx->device));
-	std::unique_ptr<op_matches> m(new op_matches);
+	MatchesPtr m(new op_matches, op_matches_free);
 	m->npairs = a->npairs + b->npairs;
 	m->count = a->count; m->count.insert(m->count.end(), b->count.begin(), b->count.end());
 	m->offset.assign(m->npairs + 1, 0);
@@ -932,11 +928,14 @@ int op_matches_concat(op_ctx* ctx, const op_matches* a, const op_matches* b, op_
 	if (resident && m->total) {
 		if (a->total && a->stream != ctx->stream) HIPCHK(hipStreamSynchronize(a->stream));     // the per-pair sort that fills a list is only ordered on its own stream
 		if (b->total && b->stream != ctx->stream) HIPCHK(hipStreamSynchronize(b->stream));
-		HIPCHK(pool_alloc((void**)&m->d_idx, sizeof(int) * 2 * (size_t)m->total));
-		if (a->total) HIPCHK(hipMemcpyAsync(m->d_idx, a->d_idx, sizeof(int) * 2 * (size_t)a->total, hipMemcpyDeviceToDevice, ctx->stream));
-		if (b->total) HIPCHK(hipMemcpyAsync(m->d_idx + 2 * a->total, b->d_idx, sizeof(int) * 2 * (size_t)b->total, hipMemcpyDeviceToDevice, ctx->stream));
+		CallBlocks own({ctx->stream});
+		int* d_idx = nullptr;
+		HIPCHK(own.alloc(&d_idx, sizeof(int) * 2 * (size_t)m->total));
+		if (a->total) HIPCHK(hipMemcpyAsync(d_idx, a->d_idx, sizeof(int) * 2 * (size_t)a->total, hipMemcpyDeviceToDevice, ctx->stream));
+		if (b->total) HIPCHK(hipMemcpyAsync(d_idx + 2 * a->total, b->d_idx, sizeof(int) * 2 * (size_t)b->total, hipMemcpyDeviceToDevice, ctx->stream));
 		HIPCHK(hipEventCreateWithFlags(&m->produced, hipEventDisableTiming));
 		HIPCHK(hipEventRecord(m->produced, ctx->stream));
+		m->d_idx = own.release(d_idx);
 	}
 	// the host mirror comes along when both sides already have theirs (a job that gathers its lists has fetched them)
 	bool both_host;

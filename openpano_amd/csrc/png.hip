@@ -46,8 +46,6 @@ struct op_png {
 
 namespace {
 
-struct Freer { std::vector<void*> v; ~Freer() { for (void* p : v) pool_free(p); } };
-
 // ------------------------------------------------ filter ------------------------------------------------
 __device__ __forceinline__ int px(const float* p, long long i) { const float v = p[i]; return (int)(unsigned char)((v < 0 ? 1.f : v) * 255.f); }
 __device__ __forceinline__ int px(const unsigned char* p, long long i) { return (int)p[i]; }
@@ -487,23 +485,22 @@ __global__ void __launch_bounds__(256) k_png_pack(const unsigned char* __restric
 	}
 }
 
-// src: device H x W x 3, fp32 canvas or bytes
-int encode_device(op_ctx* ctx, const void* src, bool is_float, int h, int w, op_png** out, const char* who) {
+// src: device H x W x 3, fp32 canvas or bytes; own: the call's blocks (on ctx->stream)
+int encode_device(op_ctx* ctx, CallBlocks& own, const void* src, bool is_float, int h, int w, op_png** out, const char* who) {
 	const long long N = (long long)h * (1 + 3LL * w);
 	if (N > (1LL << 32)) OP_FAIL(OP_ERR_UNSUPPORTED, std::string(who) + ": filtered stream above 4 GiB");
 	const int nseg = (int)((N + PNG_SEG - 1) / PNG_SEG);
 	const size_t cap = (size_t)PNG_HEAD_BYTES + (size_t)N + (size_t)nseg * (12 + 5) + 16 + 12;
 	hipStream_t st = ctx->stream;
-	Freer fr;
 	unsigned char *F = nullptr, *slots = nullptr, *obuf = nullptr; uint16_t* cand = nullptr; uint32_t *syms = nullptr, *meta = nullptr;
 	unsigned long long* total = nullptr;
-	HIPCHK(pool_alloc((void**)&F, (size_t)N)); fr.v.push_back(F);
-	HIPCHK(pool_alloc((void**)&cand, sizeof(uint16_t) * (size_t)nseg * PNG_SEG)); fr.v.push_back(cand);
-	HIPCHK(pool_alloc((void**)&syms, sizeof(uint32_t) * (size_t)nseg * PNG_SEG)); fr.v.push_back(syms);
-	HIPCHK(pool_alloc((void**)&slots, (size_t)nseg * PNG_SLOT)); fr.v.push_back(slots);
-	HIPCHK(pool_alloc((void**)&meta, sizeof(uint32_t) * 3 * (size_t)nseg)); fr.v.push_back(meta);
-	HIPCHK(pool_alloc((void**)&obuf, cap)); fr.v.push_back(obuf);
-	HIPCHK(pool_alloc((void**)&total, sizeof(unsigned long long))); fr.v.push_back(total);
+	HIPCHK(own.alloc(&F, (size_t)N));
+	HIPCHK(own.alloc(&cand, sizeof(uint16_t) * (size_t)nseg * PNG_SEG));
+	HIPCHK(own.alloc(&syms, sizeof(uint32_t) * (size_t)nseg * PNG_SEG));
+	HIPCHK(own.alloc(&slots, (size_t)nseg * PNG_SLOT));
+	HIPCHK(own.alloc(&meta, sizeof(uint32_t) * 3 * (size_t)nseg));
+	HIPCHK(own.alloc(&obuf, cap));
+	HIPCHK(own.alloc(&total, sizeof(unsigned long long)));
 	uint32_t *sizes = meta, *ad_a = meta + nseg, *ad_b = meta + 2 * (size_t)nseg;
 	HIPCHK(hipFuncSetAttribute((const void*)k_png_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DeflateLds)));   // idempotent
 	{ ProfScope ps(ctx, "png filter");
@@ -520,15 +517,13 @@ int encode_device(op_ctx* ctx, const void* src, bool is_float, int h, int w, op_
 	HIPCHK(hipMemcpyAsync(&n, total, sizeof(n), hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	if (n < PNG_HEAD_BYTES || n > cap) OP_FAIL(OP_ERR_HIP, std::string(who) + ": the device reported an impossible file size");
-	op_png* png = new op_png;
+	std::unique_ptr<op_png, void (*)(op_png*)> png(new op_png, op_png_free);
 	png->bytes.resize((size_t)n);
-	hipError_t e;
 	{ ProfScope ps(ctx, "png D2H");
-	  e = hipMemcpyAsync(png->bytes.data(), obuf, (size_t)n, hipMemcpyDeviceToHost, st); }
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e != hipSuccess) { delete png; OP_FAIL(OP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+	  HIPCHK(hipMemcpyAsync(png->bytes.data(), obuf, (size_t)n, hipMemcpyDeviceToHost, st)); }
+	HIPCHK(own.finish());
 	resolve_profile(ctx);
-	*out = png;
+	*out = png.release();
 	return OP_OK;
 }
 
@@ -542,7 +537,8 @@ int op_canvas_encode_png(op_ctx* ctx, const op_canvas* c, op_png** out) {
 	if (op_canvas_dims(c, &h, &w) != OP_OK) return OP_ERR_INVALID;
 	if (h < 1 || w < 1) OP_FAIL(OP_ERR_INVALID, "op_canvas_encode_png: empty canvas (h = 0 or w = 0): a PNG cannot hold a zero-sized image");
 	HIPCHK(hipSetDevice(ctx->device));
-	return encode_device(ctx, op_canvas_device(c), true, h, w, out, "op_canvas_encode_png");
+	CallBlocks own({ctx->stream});
+	return encode_device(ctx, own, op_canvas_device(c), true, h, w, out, "op_canvas_encode_png");
 }
 
 int op_png_encode_u8(op_ctx* ctx, const unsigned char* rgb_host, int h, int w, op_png** out) {
@@ -550,11 +546,11 @@ int op_png_encode_u8(op_ctx* ctx, const unsigned char* rgb_host, int h, int w, o
 	if (h < 1 || w < 1) OP_FAIL(OP_ERR_INVALID, "op_png_encode_u8: empty image (h = 0 or w = 0): a PNG cannot hold a zero-sized image");
 	HIPCHK(hipSetDevice(ctx->device));
 	const size_t n = (size_t)h * w * 3;
-	Freer fr;
+	CallBlocks own({ctx->stream});
 	unsigned char* d = nullptr;
-	HIPCHK(pool_alloc((void**)&d, n)); fr.v.push_back(d);
+	HIPCHK(own.alloc(&d, n));
 	HIPCHK(hipMemcpyAsync(d, rgb_host, n, hipMemcpyHostToDevice, ctx->stream));
-	return encode_device(ctx, d, false, h, w, out, "op_png_encode_u8");
+	return encode_device(ctx, own, d, false, h, w, out, "op_png_encode_u8");
 }
 
 int64_t op_png_size(const op_png* p) { return p ? (int64_t)p->bytes.size() : 0; }

@@ -21,7 +21,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <omp.h>
 
 struct op_features;
@@ -579,10 +578,8 @@ int op_ransac_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, con
 	const int2* best = (const int2*)(down + r_best);
 	const unsigned short* best_samp = (const unsigned short*)(down + r_bsamp);
 	const double* coor_host = nullptr;
-	int rc = OP_OK;
-#define RCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); rc = OP_ERR_HIP; goto done; } } while (0)
 	{
-		RCHK(ctx->ransac_arena.ensure(arena_bytes));
+		HIPCHK(ctx->ransac_arena.ensure(arena_bytes));
 		char* arena = (char*)ctx->ransac_arena.p;
 		const PairArgs* d_pa = (const PairArgs*)(arena + o_up + u_pa);
 		const unsigned* d_seeds = (const unsigned*)(arena + o_up + u_seeds);
@@ -596,7 +593,7 @@ int op_ransac_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, con
 		int* d_done = (int*)(arena + o_done);
 		const double2* d_coor = (const double2*)op_features_coor_device(f);
 		const dim3 hyp_x((iters + 255) / 256);
-		RCHK(hipMemcpyAsync(arena + o_up, pin, up_bytes, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(arena + o_up, pin, up_bytes, hipMemcpyHostToDevice, st));
 		// pairs below the match-count gate never get a workgroup: launching groups that exit at once costs more
 		// dispatcher time than the live ones compute (config 4: 703 pairs, ~640 live)
 		auto launch_group = [&](hipStream_t s, int slot_base, int n) {
@@ -608,21 +605,24 @@ int op_ransac_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, con
 		{
 			ProfScope ps(ctx, "ransac kernels (both streams)");
 			const bool fork = n_small > 0 && n_large > 0;
+			StreamJoin aux;                                                  // an exit between fork and join waits for the second stream, which writes the arena
 			if (fork) {
-				RCHK(ctx->aux());
-				RCHK(hipEventRecord(ctx->aux_fork, st));                     // the upload (and whatever made the inputs) is in front of both groups
-				RCHK(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
-				RCHK(launch_group(ctx->aux_stream, n_large, n_small));       // the long tables first
-				RCHK(hipEventRecord(ctx->aux_join, ctx->aux_stream));
-				RCHK(launch_group(st, 0, n_large));
-				RCHK(hipStreamWaitEvent(st, ctx->aux_join, 0));
-			} else RCHK(launch_group(st, 0, nactive));
+				HIPCHK(ctx->aux());
+				aux.stream = ctx->aux_stream; aux.armed = true;
+				HIPCHK(hipEventRecord(ctx->aux_fork, st));                     // the upload (and whatever made the inputs) is in front of both groups
+				HIPCHK(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
+				HIPCHK(launch_group(ctx->aux_stream, n_large, n_small));       // the long tables first
+				HIPCHK(hipEventRecord(ctx->aux_join, ctx->aux_stream));
+				HIPCHK(launch_group(st, 0, n_large));
+				HIPCHK(hipStreamWaitEvent(st, ctx->aux_join, 0));
+				aux.armed = false;
+			} else HIPCHK(launch_group(st, 0, nactive));
 		}
-		RCHK(hipMemcpyAsync(pin + up_bytes, arena + o_down, down_bytes, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(pin + up_bytes, arena + o_down, down_bytes, hipMemcpyDeviceToHost, st));
 		// the acceptance gates count the keypoints of both images inside the overlap polygon (:191-199): every
 		// coordinate of the job, fetched once per op_features (the first call waits for it; later ones find it)
 		coor_host = op_features_coor_host(f, ctx);
-		if (!coor_host) { rc = OP_ERR_HIP; goto done; }
+		if (!coor_host) return OP_ERR_HIP;
 		// what the epilogue needs besides the kernels' results is made while they run: where every pair's points and keypoints
 		// will be, and the order the pairs are judged in (below)
 		{
@@ -635,7 +635,7 @@ int op_ransac_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, con
 		}
 		order = h_active;
 		std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ph[a].m > ph[b].m; });
-		RCHK(hipStreamSynchronize(st));
+		HIPCHK(hipStreamSynchronize(st));
 	}
 	resolve_profile(ctx);
 	hs.reset(); hs.reset(new HostScope(ctx, "ransac acceptance epilogue (host)"));
@@ -699,10 +699,6 @@ int op_ransac_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, con
 		std::memcpy(it.homo, homo, sizeof(homo));
 		it.ok = 1;
 	}, 4);
-done:
-	hs.reset();
-#undef RCHK
-	if (rc != OP_OK) return rc;
 	*out = R.release();
 	return OP_OK;
 }

@@ -9,32 +9,13 @@
 #include <cmath>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <thread>
 
 size_t pyramid_lds_bytes(int halo);
 
-namespace {
-
-struct DevBuf {
-	void* p = nullptr; size_t cap = 0;
-	hipError_t ensure(size_t bytes) {
-		if (bytes <= cap) return hipSuccess;
-		if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-		size_t want = bytes + bytes / 8;
-		hipError_t e = hipMalloc(&p, want);
-		if (e != hipSuccess) return e;
-		cap = want;
-		return hipSuccess;
-	}
-	void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-};
-
-}	// namespace
-
 struct Workspace {
-	DevBuf ws, work, srcs, staging, raw, counts, refinedA, refinedB, slot_of, dirs, ndirs, oriented;
+	DevScratch ws, work, srcs, staging, raw, counts, refinedA, refinedB, slot_of, dirs, ndirs, oriented;
 	void* pinned = nullptr; size_t pinned_cap = 0;   // host-pinned scratch: source pointer table, counter block
 	std::vector<const void*> srcs_last; void* srcs_dev = nullptr;   // the pointer table the device holds (and where)
 	long long last_total = 0;                        // descriptors of the previous batch: predicts output capacity
@@ -90,6 +71,18 @@ struct op_features {
 	// op_ransac_pairs walks every keypoint of both images; features are immutable, so one copy serves every call)
 	mutable std::vector<double> h_coor; mutable bool h_coor_valid = false; mutable std::mutex h_mu;
 };
+
+using FeaturesPtr = std::unique_ptr<op_features, void (*)(op_features*)>;       // a result handle is owned from birth
+// n images, counts / offsets zeroed or (counts given) filled; null + error set on a negative count
+static FeaturesPtr new_features(int n, int device, const int* counts = nullptr) {
+	FeaturesPtr f(new op_features, op_features_free);
+	f->n = n; f->counts.assign(n, 0); f->offsets.assign(n + 1, 0); f->device = device;
+	for (int i = 0; counts && i < n; ++i) {
+		if (counts[i] < 0) { op_set_error("negative count"); f.reset(); break; }
+		f->counts[i] = counts[i]; f->offsets[i + 1] = f->offsets[i] + counts[i];
+	}
+	return f;
+}
 
 struct FeatView { int n; const int* counts; const int64_t* offsets; const float* desc; int device; };
 FeatView op_features_view(const op_features* f) {
@@ -240,15 +233,24 @@ int build_plan(const op_config& cfg, int n, int sh, int sw, SiftPlan& p, int num
 	return OP_OK;
 }
 
+// What run_group leaves.  The blocks belong to the call's CallBlocks until dropped (a re-run) or handed to the op_features it returns
 struct GroupResult {
 	std::vector<int> counts;          // per image of the group
-	float* desc = nullptr; double* coor = nullptr; double* real = nullptr;   // device (hipMalloc), group-local flat
+	float* desc = nullptr; double* coor = nullptr; double* real = nullptr;   // device (pool), group-local flat
 	long long total = 0;
+	hipError_t alloc(CallBlocks& own, size_t rows, bool with_desc = true, bool with_real = true) {       // rows x (128 fp32, 2 fp64, 2 fp64)
+		hipError_t e = own.alloc(&desc, with_desc ? sizeof(float) * 128 * rows : sizeof(float));
+		if (e == hipSuccess) e = own.alloc(&coor, sizeof(double) * 2 * rows);
+		return e == hipSuccess && with_real ? own.alloc(&real, sizeof(double) * 2 * rows) : e;
+	}
+	void drop(CallBlocks& own) { own.free(desc); own.free(coor); own.free(real); }      // only behind a wait for the stream
+	void hand_to(op_features* f, CallBlocks& own) { f->desc = own.release(desc); f->coor = own.release(coor); f->real = own.release(real); }
+	int deliver(FeaturesPtr& f, CallBlocks& own, op_features** out) { HIPCHK(own.finish()); hand_to(f.get(), own); *out = f.release(); return OP_OK; }      // a call's last line
 };
 
 // Run the whole pipeline for images of one size. `keep` (staged dump) additionally copies the
 // intermediate lists to the host.
-int run_group(op_ctx* ctx, const op_config& cfg, const std::vector<const op_image*>& imgs, Workspace& W,
+int run_group(op_ctx* ctx, CallBlocks& own, const op_config& cfg, const std::vector<const op_image*>& imgs, Workspace& W,
 		SiftPlan& plan, GroupResult& res, op_sift_dump* keep) {
 	const int n = (int)imgs.size();
 	const int sh = imgs[0]->h, sw = imgs[0]->w;
@@ -351,9 +353,7 @@ int run_group(op_ctx* ctx, const op_config& cfg, const std::vector<const op_imag
 	long long total = 0;
 	for (int attempt = 0; attempt < 2; ++attempt) {
 		HIPCHK(W.oriented.ensure(sizeof(KeyPoint) * (size_t)capK));
-		HIPCHK(pool_alloc((void**)&res.desc, sizeof(float) * 128 * (size_t)capK));
-		HIPCHK(pool_alloc((void**)&res.coor, sizeof(double) * 2 * (size_t)capK));
-		HIPCHK(pool_alloc((void**)&res.real, sizeof(double) * 2 * (size_t)capK));
+		HIPCHK(res.alloc(own, (size_t)capK));
 		{ ProfScope ps(ctx, "orientation");
 		  HIPCHK(launch_expand_oriented(plan, (const KeyPoint*)W.refinedB.p, (const int*)W.slot_of.p, d_refined_count, cap, (const float*)W.dirs.p,
 					(const int*)W.ndirs.p, d_ocnt, d_total, d_oriented_count, (KeyPoint*)W.oriented.p, capK, st)); }
@@ -363,7 +363,7 @@ int run_group(op_ctx* ctx, const op_config& cfg, const std::vector<const op_imag
 		HIPCHK(hipStreamSynchronize(st));
 		total = *h_total;
 		if (total <= capK) break;
-		pool_free(res.desc); pool_free(res.coor); pool_free(res.real); res.desc = nullptr; res.coor = nullptr; res.real = nullptr;
+		res.drop(own);
 		capK = total;                                   // exact size, second and last attempt
 	}
 	resolve_profile(ctx);
@@ -378,9 +378,9 @@ int run_group(op_ctx* ctx, const op_config& cfg, const std::vector<const op_imag
 		for (int i = 0; i < n; ++i) mx = std::max(mx, raw_count[i]);
 		if (mx > cap) {
 			if (mx > (1 << 26)) OP_FAIL(OP_ERR_CAPACITY, "raw extrema list overflow: " + std::to_string(mx));
-			pool_free(res.desc); pool_free(res.coor); pool_free(res.real); res.desc = nullptr; res.coor = nullptr; res.real = nullptr;
+			res.drop(own);
 			W.raw_cap = mx + mx / 4 + 64;          // counts are deterministic: the re-run cannot overflow again
-			return run_group(ctx, cfg, imgs, W, plan, res, keep);
+			return run_group(ctx, own, cfg, imgs, W, plan, res, keep);
 		}
 	}
 
@@ -422,45 +422,40 @@ int op_sift_batch(op_ctx* ctx, const op_config* cfg, const op_image* imgs, int n
 		if (!found) groups.push_back({key, {i}});
 	}
 	Workspace* W = ctx_workspace(ctx);
-	op_features* f = new op_features;
-	f->n = n; f->counts.assign(n, 0); f->offsets.assign(n + 1, 0); f->device = ctx->device;
+	FeaturesPtr f = new_features(n, ctx->device);
+	CallBlocks own({ctx->stream});
 	std::vector<GroupResult> results(groups.size());
 	for (size_t g = 0; g < groups.size(); ++g) {
 		std::vector<const op_image*> gi;
 		for (int idx : groups[g].second) gi.push_back(&imgs[idx]);
 		SiftPlan plan;
-		int rc = run_group(ctx, *cfg, gi, *W, plan, results[g], nullptr);
-		if (rc != OP_OK) {
-			for (auto& r : results) { pool_free(r.desc); pool_free(r.coor); pool_free(r.real); }
-			delete f; return rc;
-		}
+		int rc = run_group(ctx, own, *cfg, gi, *W, plan, results[g], nullptr);
+		if (rc != OP_OK) return rc;
 		for (size_t k = 0; k < gi.size(); ++k) f->counts[groups[g].second[k]] = results[g].counts[k];
 	}
 	int64_t total = 0;
 	for (int i = 0; i < n; ++i) { f->offsets[i] = total; total += f->counts[i]; }
 	f->offsets[n] = total;
-	if (groups.size() == 1) {
-		f->desc = results[0].desc; f->coor = results[0].coor; f->real = results[0].real;
-	} else {
-		HIPCHK(pool_alloc((void**)&f->desc, sizeof(float) * 128 * (size_t)std::max<int64_t>(total, 1)));
-		HIPCHK(pool_alloc((void**)&f->coor, sizeof(double) * 2 * (size_t)std::max<int64_t>(total, 1)));
-		HIPCHK(pool_alloc((void**)&f->real, sizeof(double) * 2 * (size_t)std::max<int64_t>(total, 1)));
+	GroupResult all;                              // several groups: their results in image order
+	if (groups.size() == 1) own.settled();        // run_group ends behind a wait for the stream
+	else {
+		HIPCHK(all.alloc(own, (size_t)std::max<int64_t>(total, 1)));
 		for (size_t g = 0; g < groups.size(); ++g) {
 			long long go = 0;
 			for (size_t k = 0; k < groups[g].second.size(); ++k) {
 				int idx = groups[g].second[k]; int c = results[g].counts[k];
 				if (c) {
-					HIPCHK(hipMemcpyAsync(f->desc + f->offsets[idx] * 128, results[g].desc + go * 128, sizeof(float) * 128 * c, hipMemcpyDeviceToDevice, ctx->stream));
-					HIPCHK(hipMemcpyAsync(f->coor + f->offsets[idx] * 2, results[g].coor + go * 2, sizeof(double) * 2 * c, hipMemcpyDeviceToDevice, ctx->stream));
-					HIPCHK(hipMemcpyAsync(f->real + f->offsets[idx] * 2, results[g].real + go * 2, sizeof(double) * 2 * c, hipMemcpyDeviceToDevice, ctx->stream));
+					HIPCHK(hipMemcpyAsync(all.desc + f->offsets[idx] * 128, results[g].desc + go * 128, sizeof(float) * 128 * c, hipMemcpyDeviceToDevice, ctx->stream));
+					HIPCHK(hipMemcpyAsync(all.coor + f->offsets[idx] * 2, results[g].coor + go * 2, sizeof(double) * 2 * c, hipMemcpyDeviceToDevice, ctx->stream));
+					HIPCHK(hipMemcpyAsync(all.real + f->offsets[idx] * 2, results[g].real + go * 2, sizeof(double) * 2 * c, hipMemcpyDeviceToDevice, ctx->stream));
 				}
 				go += c;
 			}
 		}
-		HIPCHK(hipStreamSynchronize(ctx->stream));
-		for (auto& r : results) { pool_free(r.desc); pool_free(r.coor); pool_free(r.real); }
+		HIPCHK(own.finish());
 	}
-	*out = f;
+	(groups.size() == 1 ? results[0] : all).hand_to(f.get(), own);
+	*out = f.release();
 	return OP_OK;
 }
 
@@ -500,24 +495,16 @@ int op_sift_batch_host(op_ctx* ctx, const op_config* cfg, const op_image* imgs, 
 	ptrdiff_t hstride = n > 1 ? (const char*)imgs[1].data - (const char*)imgs[0].data : (ptrdiff_t)img_bytes;
 	bool strided = hstride >= (ptrdiff_t)img_bytes;
 	for (int i = 2; i < n && strided; ++i) strided = (const char*)imgs[i].data - (const char*)imgs[i - 1].data == hstride;
-	std::vector<hipEvent_t> ev(nchunks, nullptr);
 	std::vector<GroupResult> results(nchunks);
-	std::unique_ptr<op_features, void (*)(op_features*)> f(new op_features, op_features_free);
-	f->n = n; f->counts.assign(n, 0); f->offsets.assign(n + 1, 0); f->device = ctx->device;
-	int rc = OP_OK;
-	auto cleanup = [&] {
-		hipStreamSynchronize(ctx->h2d_stream); hipStreamSynchronize(ctx->d2h_stream); hipStreamSynchronize(ctx->stream);
-		for (auto& r : results) { pool_free(r.desc); pool_free(r.coor); pool_free(r.real); r.desc = nullptr; r.coor = nullptr; r.real = nullptr; }
-		for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-	};
-#define PCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); cleanup(); return OP_ERR_HIP; } } while (0)
+	FeaturesPtr f = new_features(n, ctx->device);
+	CallBlocks own({ctx->h2d_stream, ctx->d2h_stream, ctx->stream});       // the chunk results, the table of the batch, the events
 	for (int k = 0; k < nchunks; ++k) {
 		char* dst = (char*)W->staging.p + (size_t)cb[k] * img_stride;
 		const int m = cb[k + 1] - cb[k];
-		if (strided) PCHK(hipMemcpy2DAsync(dst, img_stride, imgs[cb[k]].data, (size_t)hstride, img_bytes, (size_t)m, hipMemcpyHostToDevice, ctx->h2d_stream));
-		else for (int i = 0; i < m; ++i) PCHK(hipMemcpyAsync(dst + (size_t)i * img_stride, imgs[cb[k] + i].data, img_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
-		PCHK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-		PCHK(hipEventRecord(ev[k], ctx->h2d_stream));
+		if (strided) HIPCHK(hipMemcpy2DAsync(dst, img_stride, imgs[cb[k]].data, (size_t)hstride, img_bytes, (size_t)m, hipMemcpyHostToDevice, ctx->h2d_stream));
+		else for (int i = 0; i < m; ++i) HIPCHK(hipMemcpyAsync(dst + (size_t)i * img_stride, imgs[cb[k] + i].data, img_bytes, hipMemcpyHostToDevice, ctx->h2d_stream));
+		HIPCHK(own.event());
+		HIPCHK(hipEventRecord(own.events.back(), ctx->h2d_stream));
 	}
 	int64_t rows = 0;
 	bool overflow = false;
@@ -529,38 +516,37 @@ int op_sift_batch_host(op_ctx* ctx, const op_config* cfg, const op_image* imgs, 
 			dev[i] = imgs[cb[k] + i]; dev[i].data = (char*)W->staging.p + (size_t)(cb[k] + i) * img_stride; dev[i].on_device = 1;
 			gi[i] = &dev[i];
 		}
-		PCHK(hipStreamWaitEvent(ctx->stream, ev[k], 0));
+		HIPCHK(hipStreamWaitEvent(ctx->stream, own.events[k], 0));
 		SiftPlan plan;
-		rc = run_group(ctx, *cfg, gi, *W, plan, results[k], nullptr);
-		if (rc != OP_OK) { cleanup(); return rc; }
+		int rc = run_group(ctx, own, *cfg, gi, *W, plan, results[k], nullptr);
+		if (rc != OP_OK) return rc;
 		for (int i = 0; i < m; ++i) f->counts[cb[k] + i] = results[k].counts[i];
 		const int64_t t = results[k].total;
 		if ((desc_out || coor_out) && rows + t > capacity_rows) overflow = true;
 		if (!overflow && t) {
-			if (desc_out) PCHK(hipMemcpyAsync(desc_out + rows * 128, results[k].desc, sizeof(float) * 128 * (size_t)t, hipMemcpyDeviceToHost, ctx->d2h_stream));
-			if (coor_out) PCHK(hipMemcpyAsync(coor_out + rows * 2, results[k].coor, sizeof(double) * 2 * (size_t)t, hipMemcpyDeviceToHost, ctx->d2h_stream));
+			if (desc_out) HIPCHK(hipMemcpyAsync(desc_out + rows * 128, results[k].desc, sizeof(float) * 128 * (size_t)t, hipMemcpyDeviceToHost, ctx->d2h_stream));
+			if (coor_out) HIPCHK(hipMemcpyAsync(coor_out + rows * 2, results[k].coor, sizeof(double) * 2 * (size_t)t, hipMemcpyDeviceToHost, ctx->d2h_stream));
 		}
 		rows += t;
 	}
 	for (int i = 0; i < n; ++i) f->offsets[i + 1] = f->offsets[i] + f->counts[i];
 	{	// the resident table of the whole batch (the matcher's input): chunk results back to back
 		const size_t cnt = (size_t)std::max<int64_t>(rows, 1);
-		PCHK(pool_alloc((void**)&f->desc, sizeof(float) * 128 * cnt));
-		PCHK(pool_alloc((void**)&f->coor, sizeof(double) * 2 * cnt));
-		PCHK(pool_alloc((void**)&f->real, sizeof(double) * 2 * cnt));
+		GroupResult all;
+		HIPCHK(all.alloc(own, cnt));
 		int64_t o = 0;
 		for (int k = 0; k < nchunks; ++k) {
 			const size_t t = (size_t)results[k].total;
 			if (t) {
-				PCHK(hipMemcpyAsync(f->desc + o * 128, results[k].desc, sizeof(float) * 128 * t, hipMemcpyDeviceToDevice, ctx->stream));
-				PCHK(hipMemcpyAsync(f->coor + o * 2, results[k].coor, sizeof(double) * 2 * t, hipMemcpyDeviceToDevice, ctx->stream));
-				PCHK(hipMemcpyAsync(f->real + o * 2, results[k].real, sizeof(double) * 2 * t, hipMemcpyDeviceToDevice, ctx->stream));
+				HIPCHK(hipMemcpyAsync(all.desc + o * 128, results[k].desc, sizeof(float) * 128 * t, hipMemcpyDeviceToDevice, ctx->stream));
+				HIPCHK(hipMemcpyAsync(all.coor + o * 2, results[k].coor, sizeof(double) * 2 * t, hipMemcpyDeviceToDevice, ctx->stream));
+				HIPCHK(hipMemcpyAsync(all.real + o * 2, results[k].real, sizeof(double) * 2 * t, hipMemcpyDeviceToDevice, ctx->stream));
 			}
 			o += (int64_t)t;
 		}
+		HIPCHK(own.finish());
+		all.hand_to(f.get(), own);
 	}
-#undef PCHK
-	cleanup();
 	*out = f.release();
 	if (overflow) OP_FAIL(OP_ERR_CAPACITY, "op_sift_batch_host: " + std::to_string(rows) + " descriptors, room for " + std::to_string(capacity_rows) + " (the resident features are returned)");
 	return OP_OK;
@@ -610,59 +596,50 @@ int op_features_copy_real(op_ctx* ctx, const op_features* f, int i, double* real
 int op_features_from_host(op_ctx* ctx, const float* const* desc, const double* const* coor, const int* counts, int n, op_features** out) {
 	if (!ctx || (!desc && !coor) || !counts || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_features_from_host: bad argument");
 	HIPCHK(hipSetDevice(ctx->device));
-	op_features* f = new op_features;
-	f->n = n; f->counts.assign(counts, counts + n); f->offsets.assign(n + 1, 0); f->device = ctx->device;
-	int64_t total = 0;
-	for (int i = 0; i < n; ++i) { if (counts[i] < 0) { delete f; OP_FAIL(OP_ERR_INVALID, "negative count"); } f->offsets[i] = total; total += counts[i]; }
-	f->offsets[n] = total;
+	FeaturesPtr f = new_features(n, ctx->device, counts);
+	if (!f) return OP_ERR_INVALID;
+	const int64_t total = f->offsets[n];
 	f->has_desc = desc != nullptr;       // coordinates only: enough for op_ransac_pairs, rejected by op_match_pairs
-	HIPCHK(pool_alloc((void**)&f->desc, f->has_desc ? sizeof(float) * 128 * (size_t)std::max<int64_t>(total, 1) : sizeof(float)));
-	HIPCHK(pool_alloc((void**)&f->coor, sizeof(double) * 2 * (size_t)std::max<int64_t>(total, 1)));
-	HIPCHK(hipMemsetAsync(f->coor, 0, sizeof(double) * 2 * (size_t)std::max<int64_t>(total, 1), ctx->stream));
+	CallBlocks own({ctx->stream});
+	GroupResult r;
+	HIPCHK(r.alloc(own, (size_t)std::max<int64_t>(total, 1), f->has_desc, false));
+	HIPCHK(hipMemsetAsync(r.coor, 0, sizeof(double) * 2 * (size_t)std::max<int64_t>(total, 1), ctx->stream));
 	for (int i = 0; i < n; ++i) {
 		if (!counts[i]) continue;
-		if (f->has_desc) HIPCHK(hipMemcpyAsync(f->desc + f->offsets[i] * 128, desc[i], sizeof(float) * 128 * counts[i], hipMemcpyHostToDevice, ctx->stream));
-		if (coor && coor[i]) HIPCHK(hipMemcpyAsync(f->coor + f->offsets[i] * 2, coor[i], sizeof(double) * 2 * counts[i], hipMemcpyHostToDevice, ctx->stream));
+		if (f->has_desc) HIPCHK(hipMemcpyAsync(r.desc + f->offsets[i] * 128, desc[i], sizeof(float) * 128 * counts[i], hipMemcpyHostToDevice, ctx->stream));
+		if (coor && coor[i]) HIPCHK(hipMemcpyAsync(r.coor + f->offsets[i] * 2, coor[i], sizeof(double) * 2 * counts[i], hipMemcpyHostToDevice, ctx->stream));
 	}
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	*out = f;
-	return OP_OK;
+	return r.deliver(f, own, out);
 }
 
 int op_features_adopt_device(op_ctx* ctx, const float* desc_dev, const double* coor_dev, const int* counts, int n, op_features** out) {
 	if (!ctx || !desc_dev || !coor_dev || !counts || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_features_adopt_device: bad argument");
-	op_features* f = new op_features;
-	f->n = n; f->counts.assign(counts, counts + n); f->offsets.assign(n + 1, 0); f->device = ctx->device; f->owns = false;
-	int64_t total = 0;
-	for (int i = 0; i < n; ++i) { if (counts[i] < 0) { delete f; OP_FAIL(OP_ERR_INVALID, "negative count"); } f->offsets[i] = total; total += counts[i]; }
-	f->offsets[n] = total;
+	FeaturesPtr f = new_features(n, ctx->device, counts);
+	if (!f) return OP_ERR_INVALID;
+	f->owns = false;
 	f->desc = const_cast<float*>(desc_dev); f->coor = const_cast<double*>(coor_dev);
-	*out = f;
+	*out = f.release();
 	return OP_OK;
 }
 
 int op_features_from_device(op_ctx* ctx, const float* desc_dev, const double* coor_dev, const int* counts, int n, op_features** out) {
 	if (!ctx || !desc_dev || !counts || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_features_from_device: bad argument");
 	HIPCHK(hipSetDevice(ctx->device));
-	op_features* f = new op_features;
-	f->n = n; f->counts.assign(counts, counts + n); f->offsets.assign(n + 1, 0); f->device = ctx->device;
-	int64_t total = 0;
-	for (int i = 0; i < n; ++i) { if (counts[i] < 0) { delete f; OP_FAIL(OP_ERR_INVALID, "negative count"); } f->offsets[i] = total; total += counts[i]; }
-	f->offsets[n] = total;
+	FeaturesPtr f = new_features(n, ctx->device, counts);
+	if (!f) return OP_ERR_INVALID;
+	const int64_t total = f->offsets[n];
 	const size_t cnt = (size_t)std::max<int64_t>(total, 1);
-	HIPCHK(pool_alloc((void**)&f->desc, sizeof(float) * 128 * cnt));
-	HIPCHK(pool_alloc((void**)&f->coor, sizeof(double) * 2 * cnt));
-	if (total) HIPCHK(hipMemcpyAsync(f->desc, desc_dev, sizeof(float) * 128 * total, hipMemcpyDeviceToDevice, ctx->stream));
-	if (coor_dev && total) HIPCHK(hipMemcpyAsync(f->coor, coor_dev, sizeof(double) * 2 * total, hipMemcpyDeviceToDevice, ctx->stream));
-	else HIPCHK(hipMemsetAsync(f->coor, 0, sizeof(double) * 2 * cnt, ctx->stream));
-	HIPCHK(hipStreamSynchronize(ctx->stream));
-	*out = f;
-	return OP_OK;
+	CallBlocks own({ctx->stream});
+	GroupResult r;
+	HIPCHK(r.alloc(own, cnt, true, false));
+	if (total) HIPCHK(hipMemcpyAsync(r.desc, desc_dev, sizeof(float) * 128 * total, hipMemcpyDeviceToDevice, ctx->stream));
+	if (coor_dev && total) HIPCHK(hipMemcpyAsync(r.coor, coor_dev, sizeof(double) * 2 * total, hipMemcpyDeviceToDevice, ctx->stream));
+	else HIPCHK(hipMemsetAsync(r.coor, 0, sizeof(double) * 2 * cnt, ctx->stream));
+	return r.deliver(f, own, out);
 }
 
 }	// extern "C"
 
-extern "C" void op_features_free(op_features* f);
 // device-to-device copy between two contexts' devices, ordered on dst's stream (xGMI peer copy when the
 // devices differ; multi.hip enables direct peer access where the hardware allows it)
 static hipError_t copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t st) {
@@ -693,21 +670,21 @@ int op_features_allgather_blocks(op_ctx* const* ctxs, int nctx, op_features* con
 			op_ctx* dst = ctxs[k];
 			hipError_t e = hipSetDevice(dst->device);
 			if (e != hipSuccess) return fail(e, "hipSetDevice");
-			std::unique_ptr<op_features, void (*)(op_features*)> f(new op_features, op_features_free);
-			f->n = n; f->counts = counts; f->offsets = offsets; f->device = dst->device;
-			if ((e = pool_alloc((void**)&f->desc, sizeof(float) * 128 * cnt)) != hipSuccess) return fail(e, "pool_alloc");
-			if ((e = pool_alloc((void**)&f->coor, sizeof(double) * 2 * cnt)) != hipSuccess) return fail(e, "pool_alloc");
-			if ((e = pool_alloc((void**)&f->real, sizeof(double) * 2 * cnt)) != hipSuccess) return fail(e, "pool_alloc");
+			FeaturesPtr f = new_features(n, dst->device, counts.data());
+			CallBlocks own({dst->stream});
+			GroupResult r;
+			if ((e = r.alloc(own, cnt)) != hipSuccess) return fail(e, "pool_alloc");
 			for (int s = 0; s < nctx; ++s) {
 				const int src = (k + s) % nctx;                     // start with the own slice, then rotate: no hot source
 				const op_features* p = parts[src];
 				const size_t c = (size_t)(offsets[start[src + 1]] - offsets[start[src]]);
 				const int64_t o = offsets[start[src]];
-				if ((e = copy_between(f->desc + o * 128, dst->device, p->desc, p->device, sizeof(float) * 128 * c, dst->stream)) != hipSuccess) return fail(e, "peer copy");
-				if ((e = copy_between(f->coor + o * 2, dst->device, p->coor, p->device, sizeof(double) * 2 * c, dst->stream)) != hipSuccess) return fail(e, "peer copy");
-				if ((e = copy_between(f->real + o * 2, dst->device, p->real, p->device, sizeof(double) * 2 * c, dst->stream)) != hipSuccess) return fail(e, "peer copy");
+				if ((e = copy_between(r.desc + o * 128, dst->device, p->desc, p->device, sizeof(float) * 128 * c, dst->stream)) != hipSuccess) return fail(e, "peer copy");
+				if ((e = copy_between(r.coor + o * 2, dst->device, p->coor, p->device, sizeof(double) * 2 * c, dst->stream)) != hipSuccess) return fail(e, "peer copy");
+				if ((e = copy_between(r.real + o * 2, dst->device, p->real, p->device, sizeof(double) * 2 * c, dst->stream)) != hipSuccess) return fail(e, "peer copy");
 			}
-			if ((e = hipStreamSynchronize(dst->stream)) != hipSuccess) return fail(e, "hipStreamSynchronize");
+			if ((e = own.finish()) != hipSuccess) return fail(e, "hipStreamSynchronize");
+			r.hand_to(f.get(), own);
 			tables[k] = f.release();
 		});
 	for (auto& t : th) t.join();
@@ -720,17 +697,16 @@ int op_features_allgather_blocks(op_ctx* const* ctxs, int nctx, op_features* con
 // multi.hip: the whole table of f on dst's device (one peer copy per array)
 int op_features_replicate(op_ctx* dst, const op_features* src, op_features** out) {
 	HIPCHK(hipSetDevice(dst->device));
-	std::unique_ptr<op_features, void (*)(op_features*)> f(new op_features, op_features_free);
-	f->n = src->n; f->counts = src->counts; f->offsets = src->offsets; f->device = dst->device; f->has_desc = src->has_desc;
+	FeaturesPtr f = new_features(src->n, dst->device, src->counts.data());
+	f->has_desc = src->has_desc;
 	const int64_t total = src->offsets[src->n];
 	const size_t cnt = (size_t)std::max<int64_t>(total, 1);
-	HIPCHK(pool_alloc((void**)&f->desc, src->has_desc ? sizeof(float) * 128 * cnt : sizeof(float)));
-	HIPCHK(pool_alloc((void**)&f->coor, sizeof(double) * 2 * cnt));
-	if (src->has_desc) HIPCHK(copy_between(f->desc, dst->device, src->desc, src->device, sizeof(float) * 128 * (size_t)total, dst->stream));
-	HIPCHK(copy_between(f->coor, dst->device, src->coor, src->device, sizeof(double) * 2 * (size_t)total, dst->stream));
-	HIPCHK(hipStreamSynchronize(dst->stream));
-	*out = f.release();
-	return OP_OK;
+	CallBlocks own({dst->stream});
+	GroupResult r;
+	HIPCHK(r.alloc(own, cnt, src->has_desc, false));
+	if (src->has_desc) HIPCHK(copy_between(r.desc, dst->device, src->desc, src->device, sizeof(float) * 128 * (size_t)total, dst->stream));
+	HIPCHK(copy_between(r.coor, dst->device, src->coor, src->device, sizeof(double) * 2 * (size_t)total, dst->stream));
+	return r.deliver(f, own, out);
 }
 std::vector<op_features*>& op_features_replicas(op_features* f) { return f->replicas; }
 int op_features_device(const op_features* f) { return f->device; }
@@ -749,17 +725,18 @@ void op_features_free(op_features* f) {
 int op_sift_staged(op_ctx* ctx, const op_config* cfg, const op_image* img, op_sift_dump** out) {
 	if (!ctx || !cfg || !img || !img->data || !out || (img->dtype != OP_F32 && img->dtype != OP_U8)) OP_FAIL(OP_ERR_INVALID, "op_sift_staged: bad argument");
 	HIPCHK(hipSetDevice(ctx->device));
-	op_sift_dump* d = new op_sift_dump;
+	std::unique_ptr<op_sift_dump, void (*)(op_sift_dump*)> d(new op_sift_dump, op_sift_dump_free);
+	CallBlocks own({ctx->stream});
 	GroupResult res;
 	std::vector<const op_image*> gi{img};
-	int rc = run_group(ctx, *cfg, gi, d->w, d->plan, res, d);
-	if (rc == OP_OK && res.total) {
+	int rc = run_group(ctx, own, *cfg, gi, d->w, d->plan, res, d.get());
+	if (rc != OP_OK) return rc;
+	own.settled();                              // run_group ends behind a wait for the stream
+	if (res.total) {
 		d->coor01.resize((size_t)res.total * 2);
 		for (long long i = 0; i < res.total; ++i) { d->coor01[2 * i] = d->oriented[i].rx; d->coor01[2 * i + 1] = d->oriented[i].ry; }
 	}
-	pool_free(res.desc); pool_free(res.coor); pool_free(res.real);
-	if (rc != OP_OK) { d->w.release(); delete d; return rc; }
-	*out = d;
+	*out = d.release();
 	return OP_OK;
 }
 

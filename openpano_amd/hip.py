@@ -146,6 +146,7 @@ def lib():
     L.op_debug_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.op_debug_set_raw_capacity.argtypes = [C.c_void_p, C.c_int]
     L.op_debug_set_desc_list_cap.argtypes = [C.c_void_p, C.c_int]
+    L.op_debug_pool_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "op_match_pairs"):
         L.op_match_pairs.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.op_matches_count.argtypes = [C.c_void_p, C.c_int]
@@ -242,6 +243,13 @@ def lib():
 def check(rc):
     if rc != 0:
         raise OpenPanoHipError(f"libopenpano_hip error {rc}: {lib().op_last_error().decode(errors='replace')}")
+
+
+def pool_stats():
+    """test hook: (live_blocks, live_bytes, cached_bytes) of the process-wide device pool (op_debug_pool_stats)"""
+    v = [C.c_int64(), C.c_int64(), C.c_int64()]
+    check(lib().op_debug_pool_stats(*(C.byref(x) for x in v)))
+    return tuple(x.value for x in v)
 
 
 class Context:
