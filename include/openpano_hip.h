@@ -496,6 +496,30 @@ int64_t op_png_size(const op_png* p);
 int op_png_copy(op_ctx* ctx, const op_png* p, unsigned char* host);
 void op_png_free(op_png* p);
 
+/* ---- JPEG OUTPUT (additive within ABI 12) -- replaces write_rgb(fname, mat) where the build writes out.jpg: CImg's save_jpeg
+ * and libjpeg behind it (lib/imgio.cc:98-113; called by main.cc:30,233).  The canvas is quantised, colour-converted,
+ * transformed, Huffman-coded and byte-stuffed on the device; one D2H brings back the entropy-coded data.
+ * Format: baseline sequential DCT, 8 bits, JFIF 1.1, YCbCr at 4:4:4 or 4:2:0, the quantisation tables libjpeg derives from
+ * `quality` (the reference's file is quality 100, 4:2:0), the Huffman tables of ITU T.81 Annex K.3, a restart marker every
+ * 32 (4:4:4) or 8 (4:2:0) MCUs.  Every byte is what libjpeg writes for the same pixels, quality, sampling and restart
+ * interval; the pixels are op_canvas_copy_u8's bytes (Color::NO -> 255, v * 255 truncated).  The file is a function of the
+ * pixels alone: DESIGN.md section 13 gives the rules, tests/harness/jpeg_ref.c restates them serially.
+ * op_canvas_encode_jpeg: the device-resident canvas of op_blend / op_canvas_crop (lib/imgio.cc:98-113, main.cc:226-233).
+ * quality outside 1..100, an unknown subsampling or an empty canvas (h = 0 or w = 0, which op_canvas_crop can return) is
+ * OP_ERR_INVALID; h or w above 65535 (the frame header's 16-bit fields) is OP_ERR_UNSUPPORTED, before anything is allocated.
+ * op_jpeg_encode_u8: the same encoder for H x W x 3 bytes in host memory -- what write_rgb holds after its quantisation
+ * loop (lib/imgio.cc:98-113).
+ * op_jpeg_size / op_jpeg_copy: the file's length and its bytes (host must have room for op_jpeg_size bytes; lib/imgio.cc:98-113
+ * hands them to libjpeg's stdio destination).  op_jpeg_free releases the object.
+ * Threading and ownership as op_png: one call at a time per context; the caller owns the returned op_jpeg. */
+typedef struct op_jpeg op_jpeg;
+enum { OP_JPEG_444 = 0, OP_JPEG_420 = 1 };
+int op_canvas_encode_jpeg(op_ctx* ctx, const op_canvas* c, int quality, int subsampling, op_jpeg** out);
+int op_jpeg_encode_u8(op_ctx* ctx, const unsigned char* rgb_host, int h, int w, int quality, int subsampling, op_jpeg** out);
+int64_t op_jpeg_size(const op_jpeg* p);
+int op_jpeg_copy(op_ctx* ctx, const op_jpeg* p, unsigned char* host);
+void op_jpeg_free(op_jpeg* p);
+
 /* CYLINDER mode pre-warp -- replaces CylinderWarper::warp (stitch/warp.hh:47-55, warp.cc:13-75).
  * op_cyl_warp_shape is the host part (projector, output shape, offset and the keypoints, which
  * are centred coordinates updated in place: warp.cc:46-67); op_cyl_warp renders the pixels.  The image may be OP_F32 or

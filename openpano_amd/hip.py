@@ -227,6 +227,13 @@ def lib():
         L.op_png_size.argtypes = [C.c_void_p]
         L.op_png_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.op_png_free.argtypes = [C.c_void_p]
+    if hasattr(L, "op_canvas_encode_jpeg"):
+        L.op_canvas_encode_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.op_jpeg_encode_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.op_jpeg_size.restype = C.c_int64
+        L.op_jpeg_size.argtypes = [C.c_void_p]
+        L.op_jpeg_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.op_jpeg_free.argtypes = [C.c_void_p]
     L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
@@ -873,6 +880,18 @@ class Canvas:
         with open(path, "wb") as f:
             f.write(data)
 
+    def jpeg_bytes(self, quality=90, subsampling="420") -> bytes:
+        """the canvas as a baseline JPEG file (numpy_u8()'s pixels; every byte what libjpeg writes for them at this quality and
+        sampling, with restart markers), encoded on the device (op_canvas_encode_jpeg)"""
+        h = C.c_void_p()
+        check(lib().op_canvas_encode_jpeg(self.ctx.handle, self.handle, int(quality), _jpeg_subsampling(subsampling), C.byref(h)))
+        return _take_jpeg(self.ctx, h)
+
+    def write_jpeg(self, path, quality=90, subsampling="420"):
+        data = self.jpeg_bytes(quality, subsampling)
+        with open(path, "wb") as f:
+            f.write(data)
+
     def free(self):
         if self.handle:
             lib().op_canvas_free(self.handle); self.handle = None
@@ -901,6 +920,38 @@ def encode_png_u8(ctx: Context, array) -> bytes:
     h = C.c_void_p()
     check(lib().op_png_encode_u8(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], C.byref(h)))
     return _take_png(ctx, h)
+
+
+JPEG_444, JPEG_420 = 0, 1      # OP_JPEG_444, OP_JPEG_420
+
+
+def _jpeg_subsampling(s) -> int:
+    """"444" / "420" or the C enum; anything else goes to the library as it is (an int) and comes back as OP_ERR_INVALID"""
+    if isinstance(s, str):
+        if s not in ("444", "420"):
+            raise ValueError(f"subsampling: '444' or '420', got {s!r}")
+        return JPEG_444 if s == "444" else JPEG_420
+    return int(s)
+
+
+def _take_jpeg(ctx: Context, handle) -> bytes:
+    try:
+        out = np.empty(lib().op_jpeg_size(handle), np.uint8)
+        check(lib().op_jpeg_copy(ctx.handle, handle, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()
+    finally:
+        lib().op_jpeg_free(handle)
+
+
+def encode_jpeg_u8(ctx: Context, array, quality=90, subsampling="420") -> bytes:
+    """JPEG file of an (H, W, 3) uint8 array in host memory, through the device encoder (op_jpeg_encode_u8)"""
+    a = np.ascontiguousarray(array, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"encode_jpeg_u8: expected (H, W, 3) bytes, got {a.shape}")
+    h = C.c_void_p()
+    check(lib().op_jpeg_encode_u8(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], int(quality),
+                                  _jpeg_subsampling(subsampling), C.byref(h)))
+    return _take_jpeg(ctx, h)
 
 
 def blend_prepare(cfg, shapes_wh, homos, proj_method, identity_idx):

@@ -803,6 +803,36 @@ inline void hip_write_png(const char* fname, const Mat32f& mat) {
 	hip_write_png_file(fname, png);
 }
 
+// ---- write_rgb(fname, mat) for a .jpg name (lib/imgio.cc:98-113 -> CImg::save_jpeg -> libjpeg; main.cc:30,233): baseline JPEG
+// encoded on the device (op_canvas_encode_jpeg / op_jpeg_encode_u8), every byte what libjpeg writes for the same pixels,
+// quality, sampling and restart interval.  The reference's own file is quality 100 at OP_JPEG_420.
+inline void hip_write_jpeg_file(const char* fname, op_jpeg* jpg) {
+	std::vector<unsigned char> bytes((size_t)op_jpeg_size(jpg));
+	PANO_HIP_CHECK(op_jpeg_copy(HipContext::get(), jpg, bytes.data()));
+	op_jpeg_free(jpg);
+	FILE* f = fopen(fname, "wb");
+	if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
+		fprintf(stderr, "hip_write_jpeg: cannot write %s\n", fname);
+		exit(1);
+	}
+}
+// the device canvas a blend left behind (op_blend*, op_canvas_crop)
+inline void hip_write_jpeg(const char* fname, const op_canvas* canvas, int quality = 90, int subsampling = OP_JPEG_420) {
+	op_jpeg* jpg = nullptr;
+	PANO_HIP_CHECK(op_canvas_encode_jpeg(HipContext::get(), canvas, quality, subsampling, &jpg));
+	hip_write_jpeg_file(fname, jpg);
+}
+// write_rgb's signature: a matrix in host memory, quantised here exactly as write_rgb does (lib/imgio.cc:98-113)
+inline void hip_write_jpeg(const char* fname, const Mat32f& pano, int quality = 90, int subsampling = OP_JPEG_420) {
+	const size_t n = (size_t)pano.rows() * pano.cols() * 3;
+	std::vector<unsigned char> rgb(n);
+	const float* p = pano.ptr();
+	for (size_t i = 0; i < n; ++i) rgb[i] = (unsigned char)((p[i] < 0 ? 1 : p[i]) * 255);
+	op_jpeg* jpg = nullptr;
+	PANO_HIP_CHECK(op_jpeg_encode_u8(HipContext::get(), rgb.data(), pano.rows(), pano.cols(), quality, subsampling, &jpg));
+	hip_write_jpeg_file(fname, jpg);
+}
+
 #ifndef OPENPANO_WITH_REFERENCE
 inline void ConnectedImages::prepare(bool set_inverse, bool set_range) {
 	std::vector<double> hinv, ranges;

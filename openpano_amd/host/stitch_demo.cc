@@ -23,6 +23,9 @@
 // coefficients a1, a2, a3, where --gain-compensation puts its gains.
 // --png PATH (anywhere): additionally writes the panorama out.bin holds as an 8-bit RGB PNG, encoded on the device
 // (hip_write_png: write_rgb's quantisation, lib/imgio.cc:25-41); out.bin is the same with and without it.
+// --jpeg PATH [--jpeg-quality Q] [--jpeg-444] (anywhere): additionally writes the panorama out.bin holds as a baseline JPEG,
+// encoded on the device (hip_write_jpeg: write_rgb's quantisation, lib/imgio.cc:98-113); quality 90 and 4:2:0 unless told
+// otherwise; out.bin is the same with and without it.
 // --resident-views (anywhere): the images are uploaded once (HipStitcher::resident_views; bytes when every pixel is an exact
 // k / 255, fp32 otherwise) and SIFT, the overlap passes and the blend read that upload; out.bin is the same with and without it.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
@@ -39,6 +42,11 @@
 #include "pano_hip.hh"
 
 using namespace pano;
+
+// --jpeg PATH, --jpeg-quality Q, --jpeg-444
+static const char* g_jpeg_path = nullptr;
+static int g_jpeg_quality = 90;
+static bool g_jpeg_444 = false;
 
 template <typename T> static void put(FILE* f, const T* p, size_t n) { if (n && fwrite(p, sizeof(T), n, f) != n) { perror("write"); exit(1); } }
 template <typename T> static void put1(FILE* f, T v) { put(f, &v, 1); }
@@ -123,6 +131,7 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
 	if (png_path) hip_write_png(png_path, pano);
+	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
 	if (gain || vig) {
 		put(fo, st.gains.data(), st.gains.size());
 		const size_t per = st.gains.size() / n;      // 3 per image, or 3 per block
@@ -153,6 +162,7 @@ static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint
 	if (vig) put(fo, st.vignette_poly.data(), 3);
 	fclose(fo);
 	if (png_path) hip_write_png(png_path, pano);
+	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
 	fprintf(stderr, "Final Image Size: (%d, %d), %zu gains\n", pano.cols(), pano.rows(), st.gains.size());
 	return 0;
 }
@@ -170,6 +180,13 @@ int main(int argc, char** argv) {
 			else if (std::string(argv[k]) == "--vignetting") vig = true;
 			else if (std::string(argv[k]) == "--resident-views") resident = true;
 			else if (std::string(argv[k]) == "--png" && k + 1 < argc) png_path = argv[++k];
+			else if (std::string(argv[k]) == "--jpeg" && k + 1 < argc) g_jpeg_path = argv[++k];
+			else if (std::string(argv[k]) == "--jpeg-444") g_jpeg_444 = true;
+			else if (std::string(argv[k]) == "--jpeg-quality" && k + 1 < argc) {
+				if (sscanf(argv[++k], "%d", &g_jpeg_quality) != 1 || g_jpeg_quality < 1 || g_jpeg_quality > 100) {
+					fprintf(stderr, "--jpeg-quality wants an integer in [1, 100]; got %s\n", argv[k]); return 2;
+				}
+			}
 			else if (std::string(argv[k]) == "--gain-blocks" && k + 1 < argc) {
 				if (sscanf(argv[++k], "%dx%d", &gbx, &gby) != 2 || gbx < 1 || gbx > 16 || gby < 1 || gby > 16) {
 					fprintf(stderr, "--gain-blocks wants BXxBY, each in [1, 16]; got %s\n", argv[k]); return 2;
@@ -181,7 +198,7 @@ int main(int argc, char** argv) {
 		argc = m;
 	}
 	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--resident-views]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views]\n", argv[0]); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
@@ -277,6 +294,7 @@ int main(int argc, char** argv) {
 		if (vig) put(fo, poly.data(), 3);
 		fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
 		if (png_path) hip_write_png(png_path, pano);
+		if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
 	} else {
 		put1<int32_t>(fo, 0); put1<int32_t>(fo, 0);
 	}
