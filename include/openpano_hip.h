@@ -513,7 +513,7 @@ void op_png_free(op_png* p);
  * hands them to libjpeg's stdio destination).  op_jpeg_free releases the object.
  * Threading and ownership as op_png: one call at a time per context; the caller owns the returned op_jpeg. */
 typedef struct op_jpeg op_jpeg;
-enum { OP_JPEG_444 = 0, OP_JPEG_420 = 1 };
+enum { OP_JPEG_444 = 0, OP_JPEG_420 = 1, OP_JPEG_422 = 2, OP_JPEG_GREY = 3 };      /* the encoder takes the first two; op_jpeg_probe reports all four */
 int op_canvas_encode_jpeg(op_ctx* ctx, const op_canvas* c, int quality, int subsampling, op_jpeg** out);
 int op_jpeg_encode_u8(op_ctx* ctx, const unsigned char* rgb_host, int h, int w, int quality, int subsampling, op_jpeg** out);
 int64_t op_jpeg_size(const op_jpeg* p);
@@ -547,6 +547,38 @@ int op_views_count(const op_views* v);
 int op_views_image(const op_views* v, int i, op_image* out);
 int op_views_blend_image(const op_views* v, int i, op_blend_image* out);
 void op_views_free(op_views* v);
+
+/* ---- JPEG INPUT (additive within ABI 12) -- replaces read_img(fname) and the decoder behind it, CImg::load -> libjpeg
+ * (lib/imgio.cc:67-90), where ImageRef::load calls it (stitch/imageref.hh:22-27): camera files go in, resident views come
+ * out, and the decoded bytes never exist on the host.  DESIGN.md section 14 gives the format, the rules and the kernels;
+ * tests/harness/jpeg_dec_ref.c restates the decoder serially.
+ * Accepted: SOF0 (baseline sequential, Huffman, 8 bits) with one interleaved scan; three components as YCbCr at 4:4:4,
+ * 4:2:2 (21 11 11) or 4:2:0 (22 11 11), or one component (grey, written R = G = B); any 8-bit DQT and any DHT tables; DRI
+ * present or absent; APPn / COM segments of any content; bytes after EOI.  Every byte of a view is libjpeg's default decode of
+ * the file (ISLOW IDCT, fancy upsampling, JFIF YCbCr -> RGB), i.e. the bytes lib/imgio.cc:78-80 converts to float.
+ * OP_ERR_UNSUPPORTED: every other SOF, 12-bit precision, 16-bit DQT, other samplings or component counts, RGB components
+ * (an Adobe APP14 with transform 0), more than one SOS, DNL.  OP_ERR_INVALID: a structurally broken header (a segment past
+ * the end of the file, a missing SOF / DQT / DHT / SOS / EOI, a table id out of range), h or w below 2.  Both come from a
+ * host parser that reads headers only, before anything is allocated or launched.
+ * op_jpeg_probe (HOST ONLY, needs no device): parses `size` bytes at `file` and writes h, w and the sampling (OP_JPEG_444,
+ * OP_JPEG_420, OP_JPEG_422 or OP_JPEG_GREY; each may be NULL).  OP_OK, OP_ERR_UNSUPPORTED or OP_ERR_INVALID, so a caller
+ * can route a file to a decoder of its own (lib/imgio.cc:67-90).
+ * op_views_decode_jpeg: decodes n files into one op_views of OP_U8 views, indistinguishable from op_views_upload of the
+ * same bytes (stitch/imageref.hh:22-27).  All or nothing: a refused file, or one whose entropy-coded data is corrupt
+ * (OP_ERR_INVALID, found on the device), leaves *out NULL and no device memory held; op_last_error names the file's index
+ * in the batch and the reason.  The sources are free again on return.
+ * op_views_copy: view i to host memory in its own type, 3 h w bytes or floats (the read-back of ImageRef::img,
+ * stitch/imageref.hh:15-31; for tests and callers that keep a host copy).
+ * op_debug_set_jpeg_subseq_bits: test hook like op_debug_set_desc_list_cap: the bits of a subsequence of the parallel
+ * Huffman decode, a multiple of 32 from 32 to 65536, or 0 for the default (1024).  The views do not depend on it.
+ * op_debug_jpeg_last_rounds: test hook: the synchronisation rounds the last op_views_decode_jpeg on ctx needed (the
+ * largest of its files).
+ * Threading and ownership as op_views_upload: one call at a time per context; the caller frees the op_views. */
+int op_jpeg_probe(const unsigned char* file, int64_t size, int* h, int* w, int* sampling);
+int op_views_decode_jpeg(op_ctx* ctx, const unsigned char* const* files, const int64_t* sizes, int n, op_views** out);
+int op_views_copy(op_ctx* ctx, const op_views* v, int i, void* host);
+int op_debug_set_jpeg_subseq_bits(op_ctx* ctx, int bits);
+int op_debug_jpeg_last_rounds(op_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -32,12 +32,6 @@
 #include <cmath>
 #include <cstring>
 
-struct op_views {
-	op_ctx* ctx = nullptr;
-	char* block = nullptr;            // one pool block; view i at imgs[i].data, a multiple of 256 bytes into it
-	std::vector<op_image> imgs;       // device images, each in its own dtype
-};
-
 struct op_canvas {
 	float* data = nullptr;   // device, h x w x 3
 	int h = 0, w = 0;

@@ -43,6 +43,8 @@ struct op_ctx {
 	hipStream_t stream = nullptr;
 	bool owns_stream = false;
 	bool profiling = false;
+	int jpeg_subseq_bits = 0;                        // JPEG decoder: bits of a subsequence (0: JD_S_DEFAULT; op_debug_set_jpeg_subseq_bits)
+	int jpeg_last_rounds = 0;                        // pass-B rounds of the last op_views_decode_jpeg (the largest of its images)
 	std::string prof_only;                           // when not empty: only this stage is bracketed by events
 	int match_slow_seen[2] = {-1, -1};               // exact-scan rows (forward, reverse) of the previous op_match_pairs call: sizes the next launch
 	std::vector<ProfStage> prof;
@@ -145,6 +147,13 @@ struct CallBlocks {
 };
 // waits for a forked stream when its scope ends between the fork (armed) and the join (disarmed)
 struct StreamJoin { hipStream_t stream = nullptr; bool armed = false; ~StreamJoin() { if (armed) (void)hipStreamSynchronize(stream); } };
+
+// the views of a job, resident on the device (op_views_upload in blend.hip, op_views_decode_jpeg in jpeg_dec.hip)
+struct op_views {
+	op_ctx* ctx = nullptr;
+	char* block = nullptr;            // one pool block; view i at imgs[i].data, a multiple of 256 bytes into it
+	std::vector<op_image> imgs;       // device images, each in its own dtype
+};
 
 // ---------------------------------------------------------------------------------------
 // HBM layout of one image's scale space ("image workspace", ws_stride floats per image):

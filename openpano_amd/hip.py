@@ -243,6 +243,12 @@ def lib():
         L.op_views_image.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpImage)]
         L.op_views_blend_image.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpBlendImage)]
         L.op_views_free.argtypes = [C.c_void_p]
+    if hasattr(L, "op_views_decode_jpeg"):
+        L.op_jpeg_probe.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.op_views_decode_jpeg.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_void_p)]
+        L.op_views_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.op_debug_set_jpeg_subseq_bits.argtypes = [C.c_void_p, C.c_int]
+        L.op_debug_jpeg_last_rounds.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -292,6 +298,15 @@ class Context:
     def set_desc_list_cap(self, floats: int):
         """test hook: list arena one sorting pass of the descriptor kernel may use (op_debug_set_desc_list_cap)"""
         check(lib().op_debug_set_desc_list_cap(self.handle, int(floats)))
+
+    def set_jpeg_subseq_bits(self, bits: int):
+        """test hook: bits of a subsequence of the JPEG decoder's parallel Huffman decode, a multiple of 32; 0 = the default
+        (op_debug_set_jpeg_subseq_bits)"""
+        check(lib().op_debug_set_jpeg_subseq_bits(self.handle, int(bits)))
+
+    def jpeg_last_rounds(self) -> int:
+        """test hook: synchronisation rounds of the last Views.decode_jpeg on this context (op_debug_jpeg_last_rounds)"""
+        return lib().op_debug_jpeg_last_rounds(self.handle)
 
     def set_raw_capacity(self, cap: int):
         """test hook: per-image capacity of the speculative raw / refined lists (op_debug_set_raw_capacity)"""
@@ -409,6 +424,30 @@ class Views:
         del keep
         return cls(ctx, h)
 
+    @classmethod
+    def decode_jpeg(cls, ctx: Context, files) -> "Views":
+        """files: a list of baseline JPEG files as bytes; decoded on the device into uint8 views that equal libjpeg's
+        default decode byte for byte (op_views_decode_jpeg).  All or nothing: a file outside the format or a corrupt one
+        raises, naming its index."""
+        if not hasattr(lib(), "op_views_decode_jpeg"):
+            raise OpenPanoHipError("libopenpano_hip.so was built without op_views_decode_jpeg")
+        files = [bytes(f) for f in files]
+        arr = (C.c_char_p * len(files))(*files)
+        sizes = (C.c_int64 * len(files))(*[len(f) for f in files])
+        h = C.c_void_p()
+        check(lib().op_views_decode_jpeg(ctx.handle, arr, sizes, len(files), C.byref(h)))
+        return cls(ctx, h)
+
+    def numpy(self, i: int) -> np.ndarray:
+        """view i read back as (H, W, 3) in its own type, uint8 or float32 (op_views_copy)"""
+        if not hasattr(lib(), "op_views_copy"):
+            raise OpenPanoHipError("libopenpano_hip.so was built without op_views_copy")
+        im = OpImage()
+        check(lib().op_views_image(self.handle, int(i), C.byref(im)))
+        out = np.empty((im.h, im.w, 3), np.uint8 if im.dtype == OP_U8 else np.float32)
+        check(lib().op_views_copy(self.ctx.handle, self.handle, int(i), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     @property
     def count(self):
         return lib().op_views_count(self.handle)
@@ -442,6 +481,20 @@ class Views:
             self.free()
         except Exception:
             pass
+
+
+JPEG_SAMPLING_NAMES = {0: "444", 1: "420", 2: "422", 3: "grey"}
+
+
+def jpeg_probe(data):
+    """(h, w, sampling) of a JPEG file that ``Views.decode_jpeg`` accepts, sampling one of "444", "422", "420", "grey";
+    raises OpenPanoHipError (error -4: outside the format, -1: broken) otherwise.  Host only: needs no device."""
+    if not hasattr(lib(), "op_jpeg_probe"):
+        raise OpenPanoHipError("libopenpano_hip.so was built without op_jpeg_probe")
+    data = bytes(data)
+    h, w, s = C.c_int(), C.c_int(), C.c_int()
+    check(lib().op_jpeg_probe(data, len(data), C.byref(h), C.byref(w), C.byref(s)))
+    return h.value, w.value, JPEG_SAMPLING_NAMES[s.value]
 
 
 def _mk_blend_images(images):

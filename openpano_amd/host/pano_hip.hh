@@ -289,8 +289,36 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 					op_features_free(fs.handle); fs.handle = nullptr;
 				}
 			}
-			fs.feats.resize(imgs.size());
-			for (size_t k = 0; k < imgs.size(); ++k) {
+			fill_feats(fs, imgs.size(), desc, coor);
+			return fs;
+		}
+
+		// The same for views that are already on the device -- decoded there by hip_read_jpeg_views, or uploaded by the
+		// caller: no host pixel is read.  The result owns `views` (HipFeatureSet::views), as calc_feature(imgs, true) owns its upload.
+		HipFeatureSet calc_feature(op_views* views) const {
+			op_ctx* ctx = HipContext::get();
+			const op_config cfg = hip_config_snapshot();
+			HipFeatureSet fs;
+			fs.views = views;
+			const int n = op_views_count(views);
+			if (n <= 0) hip_error_exit("calc_feature(op_views*)");
+			std::vector<op_image> dev((size_t)n);
+			for (int k = 0; k < n; ++k) PANO_HIP_CHECK(op_views_image(views, k, &dev[k]));
+			PANO_HIP_CHECK(op_sift_batch(ctx, &cfg, dev.data(), n, &fs.handle));
+			const size_t total = (size_t)op_features_total(fs.handle);
+			std::vector<float> desc(total * 128 + 1); std::vector<double> coor(total * 2 + 1);
+			for (int k = 0; k < n; ++k)
+				if (op_features_count(fs.handle, k))
+					PANO_HIP_CHECK(op_features_copy(ctx, fs.handle, k, desc.data() + (size_t)op_features_offset(fs.handle, k) * 128,
+							coor.data() + (size_t)op_features_offset(fs.handle, k) * 2));
+			fill_feats(fs, (size_t)n, desc, coor);
+			return fs;
+		}
+
+	private:
+		static void fill_feats(HipFeatureSet& fs, size_t nimg, const std::vector<float>& desc, const std::vector<double>& coor) {
+			fs.feats.resize(nimg);
+			for (size_t k = 0; k < nimg; ++k) {
 				const int n = op_features_count(fs.handle, (int)k);
 				if (n == 0) {    // stitcherbase.cc:20-21
 					fprintf(stderr, "Cannot find feature in image %d!\n", (int)k);
@@ -304,9 +332,30 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 					fs.feats[k][i].descriptor.assign(d + (size_t)i * 128, d + (size_t)(i + 1) * 128);
 				}
 			}
-			return fs;
 		}
 };
+
+// ImageRef::load for a job of baseline JPEG files (stitch/imageref.hh:22-27 -> read_img, lib/imgio.cc:67-90): the files are
+// read, their headers parsed on the host, and everything else -- Huffman decode, IDCT, upsampling, colour -- runs on the
+// device (op_views_decode_jpeg).  The views are bytes, every one of them libjpeg's; the caller owns the result
+// (op_views_free), or hands it to HipSIFTDetector::calc_feature(op_views*).  A file outside the format ends the program with
+// the library's message, which names its index; op_jpeg_probe tells beforehand.
+inline op_views* hip_read_jpeg_views(op_ctx* ctx, const std::vector<std::string>& paths) {
+	std::vector<std::vector<unsigned char>> data(paths.size());
+	std::vector<const unsigned char*> ptr(paths.size());
+	std::vector<int64_t> size(paths.size());
+	for (size_t k = 0; k < paths.size(); ++k) {
+		FILE* f = fopen(paths[k].c_str(), "rb");
+		if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", paths[k].c_str()); exit(1); }      // lib/imgio.cc:68-69
+		unsigned char buf[65536]; size_t n;
+		while ((n = fread(buf, 1, sizeof buf, f)) > 0) data[k].insert(data[k].end(), buf, buf + n);
+		fclose(f);
+		ptr[k] = data[k].data(); size[k] = (int64_t)data[k].size();
+	}
+	op_views* v = nullptr;
+	PANO_HIP_CHECK(op_views_decode_jpeg(ctx, ptr.data(), size.data(), (int)paths.size(), &v));
+	return v;
+}
 
 // ===================================== MATCH =====================================
 // Same public signature as the reference's PairWiseMatcher (feature/matcher.hh:40-51).  match()
@@ -651,8 +700,14 @@ inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_ge
 	for (int i = 0; i < n; ++i) {
 		auto& c = b.component[i];
 		c.imgptr->load();
-		ims[i].data = c.imgptr->img->ptr(); ims[i].h = c.imgptr->height(); ims[i].w = c.imgptr->width(); ims[i].on_device = 0;
-		ims[i].mat_h = c.imgptr->img->height(); ims[i].mat_w = c.imgptr->img->width();      // != h / w after a cylinder pre-warp (op_blend_image)
+		ims[i].h = c.imgptr->height(); ims[i].w = c.imgptr->width(); ims[i].on_device = 0;
+		if (c.imgptr->img) {
+			ims[i].data = c.imgptr->img->ptr();
+			ims[i].mat_h = c.imgptr->img->height(); ims[i].mat_w = c.imgptr->img->width();      // != h / w after a cylinder pre-warp (op_blend_image)
+		} else {    // decoded on the device (HipStitcher::jpeg_paths): the resident view is the only copy
+			ims[i].data = nullptr; ims[i].mat_h = ims[i].h; ims[i].mat_w = ims[i].w;
+			if (!views) { fprintf(stderr, "hip_blend_images: component %d has neither host pixels nor a resident view\n", i); exit(1); }
+		}
 		if (views) {    // the resident view stands for the Mat it was uploaded from; a Mat replaced since (cylinder pre-warp) keeps the host path
 			op_blend_image v;
 			PANO_HIP_CHECK(op_views_blend_image(views, i, &v));
@@ -660,6 +715,7 @@ inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_ge
 				ims[i].data = v.data; ims[i].on_device = v.on_device;
 			}
 		}
+		if (!ims[i].data) { fprintf(stderr, "hip_blend_images: resident view %d is %d x %d, its component %d x %d\n", i, ims[i].mat_w, ims[i].mat_h, ims[i].w, ims[i].h); exit(1); }
 		for (int k = 0; k < 9; ++k) ims[i].homo_inv[k] = c.homo_inv[k];
 		ims[i].range[0] = c.range.min.x; ims[i].range[1] = c.range.min.y; ims[i].range[2] = c.range.max.x; ims[i].range[3] = c.range.max.y;
 	}
@@ -946,12 +1002,36 @@ class HipStitcher {
 			for (auto& m : mats) imgs.emplace_back(m);
 			for (auto& r : imgs) bundle.component.emplace_back(&r);
 		}
+		// From camera files: jpeg_paths stands in place of the Mat32f images (ImageRef(fname), stitch/imageref.hh:15-31).  Only
+		// the headers are read here (op_jpeg_probe, for the shapes); calc_feature() decodes the files on the device
+		// (hip_read_jpeg_views) and SIFT, the overlap passes and the blend read those views: build() touches no host pixel.
+		explicit HipStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u): base_seed(base_seed), jpeg_paths(paths) {
+			if (paths.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", paths.size()); exit(1); }   // stitcherbase.hh:46-48
+			for (auto& p : paths) {
+				FILE* f = fopen(p.c_str(), "rb");
+				if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", p.c_str()); exit(1); }
+				std::vector<unsigned char> head(1 << 20);      // SOF0 comes before the scan; a megabyte holds any EXIF before it
+				const size_t got = fread(head.data(), 1, head.size(), f);
+				bool whole = got < head.size();
+				if (!whole) {
+					fseek(f, 0, SEEK_END); const long all = ftell(f); fseek(f, 0, SEEK_SET);
+					head.resize((size_t)all);
+					whole = fread(head.data(), 1, head.size(), f) == head.size();
+				} else head.resize(got);
+				fclose(f);
+				int h = 0, w = 0, sampling = 0;
+				if (!whole || op_jpeg_probe(head.data(), (int64_t)head.size(), &h, &w, &sampling) != OP_OK) hip_error_exit(p);
+				imgs.emplace_back(p);
+				imgs.back()._width = w; imgs.back()._height = h;
+			}
+			for (auto& r : imgs) bundle.component.emplace_back(&r);
+		}
 		HipStitcher(const HipStitcher&) = delete;
 		HipStitcher& operator=(const HipStitcher&) = delete;
 
 		Mat32f build() {                                            // stitcher.cc:32-64
 			calc_feature();
-			bundle.views = resident_views ? feats.views : nullptr;
+			bundle.views = resident_views || !jpeg_paths.empty() ? feats.views : nullptr;
 			pairwise_matches.assign(imgs.size(), std::vector<MatchInfo>(imgs.size()));
 			if (config::ORDERED_INPUT) linear_pairwise_match();
 			else pairwise_match();
@@ -995,12 +1075,15 @@ class HipStitcher {
 		// resident views: calc_feature uploads the images once (bytes when they are exact k / 255, fp32 otherwise) and SIFT,
 		// the overlap passes and the blend all read that upload; off by default.  The panorama is the same bit for bit.
 		bool resident_views = false;
+		// set by the constructor that takes files: the views are decoded on the device and always resident
+		std::vector<std::string> jpeg_paths;
 
 		void calc_feature() {                                       // stitcherbase.cc:9-27
 			std::vector<const Mat32f*> ptrs;
 			for (auto& r : imgs) ptrs.push_back(r.img);
 			bundle.views = nullptr;                                 // the previous upload is released by the assignment below
-			feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
+			if (!jpeg_paths.empty()) feats = HipSIFTDetector().calc_feature(hip_read_jpeg_views(HipContext::get(), jpeg_paths));
+			else feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
 			keypoints.resize(imgs.size());
 			for (size_t k = 0; k < imgs.size(); ++k) {
 				keypoints[k].clear();

@@ -28,6 +28,9 @@
 // otherwise; out.bin is the same with and without it.
 // --resident-views (anywhere): the images are uploaded once (HipStitcher::resident_views; bytes when every pixel is an exact
 // k / 255, fp32 otherwise) and SIFT, the overlap passes and the blend read that upload; out.bin is the same with and without it.
+// --jpeg-list PATH (anywhere; camera modes only): PATH is a text file with one baseline JPEG path per line.  The files stand in
+// place of in.bin's contents (in.bin is not opened) and are decoded on the device (HipStitcher over jpeg_paths,
+// hip_read_jpeg_views); implies --resident-views.  out.bin equals a run on an in.bin that holds the same decoded pixels.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
@@ -92,16 +95,15 @@ static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::
 
 // Stitcher::build() under ESTIMATE_CAMERA (stitch/stitcher.cc:32-64), stage by stage so that every
 // intermediate can be written out
-static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby,
+static int run_camera_mode(Stitcher& st, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby,
 		bool vig, const char* png_path, bool resident) {
-	Stitcher st(mats, base_seed);
 	st.resident_views = resident;
 	FILE* fo = fopen(out_path, "wb");
 	if (!fo) { perror(out_path); return 2; }
 	st.calc_feature();
 	st.bundle.views = resident ? st.feats.views : nullptr;     // what HipStitcher::build() does under resident_views
 	put_features(fo, st.feats);
-	const int n = (int)mats.size();
+	const int n = (int)st.imgs.size();
 	st.pairwise_matches.assign(n, std::vector<MatchInfo>(n));
 	std::vector<std::pair<int, int>> tasks;
 	if (ordered) for (int i = 0; i < n; ++i) tasks.emplace_back(i, (i + 1) % n);
@@ -146,9 +148,8 @@ static int run_camera_mode(const std::vector<Mat32f>& mats, const char* out_path
 }
 
 // Stitcher::build() as a client calls it, gain compensation per HipStitcher::gain_compensation
-static int run_build(const std::vector<Mat32f>& mats, const char* out_path, uint32_t base_seed, bool gain, int gbx, int gby, bool vig,
+static int run_build(Stitcher& st, const char* out_path, bool gain, int gbx, int gby, bool vig,
 		const char* png_path, bool resident) {
-	Stitcher st(mats, base_seed);
 	st.resident_views = resident;
 	st.gain_compensation = gain;
 	st.vignetting = vig;
@@ -173,12 +174,14 @@ int main(int argc, char** argv) {
 	bool vig = false;
 	const char* png_path = nullptr;
 	bool resident = false;
+	const char* jpeg_list = nullptr;
 	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
 			if (std::string(argv[k]) == "--gain-compensation") gain = true;
 			else if (std::string(argv[k]) == "--vignetting") vig = true;
 			else if (std::string(argv[k]) == "--resident-views") resident = true;
+			else if (std::string(argv[k]) == "--jpeg-list" && k + 1 < argc) { jpeg_list = argv[++k]; resident = true; }
 			else if (std::string(argv[k]) == "--png" && k + 1 < argc) png_path = argv[++k];
 			else if (std::string(argv[k]) == "--jpeg" && k + 1 < argc) g_jpeg_path = argv[++k];
 			else if (std::string(argv[k]) == "--jpeg-444") g_jpeg_444 = true;
@@ -198,8 +201,28 @@ int main(int argc, char** argv) {
 		argc = m;
 	}
 	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH]\n", argv[0]); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
+	const std::string mode = argc > 4 ? argv[4] : "";
+	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
+	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
+	config::LAZY_READ = false;
+	if (jpeg_list) {
+		if (!camera_mode) { fprintf(stderr, "--jpeg-list goes with camera, camera_ordered or camera_build\n"); return 2; }
+		std::vector<std::string> paths;
+		FILE* fl = fopen(jpeg_list, "r");
+		if (!fl) { perror(jpeg_list); return 2; }
+		char line[4096];
+		while (fgets(line, sizeof line, fl)) {
+			std::string p(line);
+			while (!p.empty() && (p.back() == '\n' || p.back() == '\r' || p.back() == ' ')) p.pop_back();
+			if (!p.empty()) paths.push_back(p);
+		}
+		fclose(fl);
+		Stitcher st(paths, base_seed);
+		if (mode == "camera_build") return run_build(st, argv[2], gain, gbx, gby, vig, png_path, resident);
+		return run_camera_mode(st, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
+	}
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
 	int32_t hdr[3];
@@ -211,12 +234,11 @@ int main(int argc, char** argv) {
 		if (fread(mats.back().ptr(), sizeof(float), (size_t)h * w * 3, fi) != (size_t)h * w * 3) return 2;
 	}
 	fclose(fi);
-	const std::string mode = argc > 4 ? argv[4] : "";
-	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
-	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
-	config::LAZY_READ = false;
-	if (mode == "camera_build") return run_build(mats, argv[2], base_seed, gain, gbx, gby, vig, png_path, resident);
-	if (camera_mode) return run_camera_mode(mats, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
+	if (camera_mode) {
+		Stitcher st(mats, base_seed);
+		if (mode == "camera_build") return run_build(st, argv[2], gain, gbx, gby, vig, png_path, resident);
+		return run_camera_mode(st, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
+	}
 
 	// ---- StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27)
 	std::vector<ImageRef> imgs;
