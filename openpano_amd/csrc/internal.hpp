@@ -7,15 +7,13 @@
 #include <string>
 #include <vector>
 #include "openpano_hip.h"
+#include "op_base.hpp"       // op_set_error, OP_FAIL, OP_MAX_KCENTER: the host-only units see them without the HIP runtime
 
 #define OP_MAX_OCT 8
 #define OP_MAX_SCALE 12      // NUM_SCALE <= 12
-#define OP_MAX_KCENTER 15    // Gaussian kernels up to 31 taps
 
-void op_set_error(const std::string& msg);
 struct op_ctx;
 void op_ctx_release_workspace(op_ctx* c);
-#define OP_FAIL(code, msg) do { op_set_error(msg); return (code); } while (0)
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	op_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return OP_ERR_HIP; } } while (0)
 
@@ -148,12 +146,23 @@ struct CallBlocks {
 // waits for a forked stream when its scope ends between the fork (armed) and the join (disarmed)
 struct StreamJoin { hipStream_t stream = nullptr; bool armed = false; ~StreamJoin() { if (armed) (void)hipStreamSynchronize(stream); } };
 
-// the views of a job, resident on the device (op_views_upload in blend.hip, op_views_decode_jpeg in jpeg_dec.hip)
+// the views of a job, resident on the device (op_views_upload in views.hip, op_views_decode_jpeg in jpeg_dec.hip)
 struct op_views {
 	op_ctx* ctx = nullptr;
 	char* block = nullptr;            // one pool block; view i at imgs[i].data, a multiple of 256 bytes into it
 	std::vector<op_image> imgs;       // device images, each in its own dtype
 };
+
+// a blended, warped or cropped image on the device (blend.hip and canvas.hip make them; canvas.hip, png.hip and jpeg.hip read them)
+struct op_canvas {
+	float* data = nullptr;   // device, h x w x 3
+	int h = 0, w = 0;
+	int device = 0;
+};
+// The byte of a canvas float: write_rgb / write_png quantisation (lib/imgio.cc:25-40,98-113), Color::NO -> white, float * 255
+// truncated.  The one expression behind op_canvas_copy_u8 and the PNG and JPEG encoders, whose files are byte-equal to the
+// reference's because of it.
+__device__ __forceinline__ unsigned char canvas_byte(float v) { return (unsigned char)((v < 0 ? 1.f : v) * 255.f); }
 
 // ---------------------------------------------------------------------------------------
 // HBM layout of one image's scale space ("image workspace", ws_stride floats per image):

@@ -3,7 +3,7 @@
 // Stands in for write_rgb -> CImg::save_jpeg -> libjpeg (lib/imgio.cc:98-113, called by main.cc:30,233): sequential DCT,
 // 8 bits, 4:4:4 or 4:2:0, the Huffman tables of ITU T.81 Annex K.3, a restart marker every OP_JPEG_RI_444 / OP_JPEG_RI_420
 // MCUs.  A restart interval is byte-aligned and starts its DC prediction at 0, so intervals are independent.  Two kernels:
-//   k_jpeg_interval  one workgroup per restart interval: quantise the canvas (k_to_u8's expression, blend.hip), RGB -> YCbCr,
+//   k_jpeg_interval  one workgroup per restart interval: quantise the canvas (canvas_byte), RGB -> YCbCr,
 //                    4:2:0 chroma averaging, IJG slow-integer forward DCT (rows, then columns), quantisation, zigzag -- all in
 //                    LDS; one thread per block counts its bits, a prefix sum places them, the codes are ORed into an LDS bit
 //                    image, a second prefix sum (of 0xFF bytes) places the stuffed bytes in the interval's slot;
@@ -83,7 +83,7 @@ __host__ __device__ inline int jpeg_q(int base, int quality) {
 	return v < 1 ? 1 : v > 255 ? 255 : v;
 }
 
-__device__ __forceinline__ int jpx(const float* p, long long i) { const float v = p[i]; return (int)(unsigned char)((v < 0 ? 1.f : v) * 255.f); }
+__device__ __forceinline__ int jpx(const float* p, long long i) { return (int)canvas_byte(p[i]); }
 __device__ __forceinline__ int jpx(const unsigned char* p, long long i) { return (int)p[i]; }
 
 template <typename T>

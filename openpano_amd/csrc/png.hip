@@ -2,7 +2,7 @@
 //
 // Stands in for write_rgb -> write_png -> lodepng::encode (lib/imgio.cc:25-41,98-113), the largest single cost of a whole
 // run of the reference's CLI.  8-bit RGB, colour type 2, no interlace: signature, IHDR, IDAT chunks, IEND.  Three kernels:
-//   k_png_filter   one workgroup per scanline: quantise (k_to_u8's expression, blend.hip) and pick the PNG filter type with
+//   k_png_filter   one workgroup per scanline: quantise (canvas_byte) and pick the PNG filter type with
 //                  the smallest sum of |residual as a signed byte|, ties to the lowest type; writes the filtered stream F;
 //   k_png_deflate  one workgroup per PNG_SEG bytes of F: hash candidates, a greedy parse of 256 sub-blocks (one per thread),
 //                  dynamic Huffman tables, bits packed at offsets from a prefix sum; or a stored block when that is not larger.
@@ -47,7 +47,7 @@ struct op_png {
 namespace {
 
 // ------------------------------------------------ filter ------------------------------------------------
-__device__ __forceinline__ int px(const float* p, long long i) { const float v = p[i]; return (int)(unsigned char)((v < 0 ? 1.f : v) * 255.f); }
+__device__ __forceinline__ int px(const float* p, long long i) { return (int)canvas_byte(p[i]); }
 __device__ __forceinline__ int px(const unsigned char* p, long long i) { return (int)p[i]; }
 __device__ __forceinline__ int paeth(int a, int b, int c) {
 	const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);

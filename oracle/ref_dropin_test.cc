@@ -118,7 +118,7 @@ static void compare_canvas(const Mat32f& a, const Mat32f& b, const char* what) {
 	}
 	printf("  %s: %dx%d, covered %.1f%%, max |diff| %.3g, bit-equal %.4f%%, mask flips %ld\n", what, a.rows(), a.cols(),
 			100.0 * valid / n, maxd, 100.0 * exact / std::max(1L, valid), mask_diff);
-	// same homographies on both sides and the map's sin / cos / tan from the host libm on both sides (csrc/blend.hip): bit-exact
+	// same homographies on both sides and the map's sin / cos / tan from the host libm on both sides (csrc/blend.hip: trig_tables): bit-exact
 	EXPECT(maxd == 0, "%s: max diff %g", what, maxd);
 	EXPECT(mask_diff == 0, "%s: %ld no-pixel mask flips", what, mask_diff);
 	EXPECT(valid > n / 3, "%s: canvas barely covered", what);

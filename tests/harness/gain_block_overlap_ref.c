@@ -1,4 +1,4 @@
-/* gain_block_overlap_ref.c -- CPU restatements of the block gain entry points (openpano_amd/csrc/blend.hip) for
+/* gain_block_overlap_ref.c -- CPU restatements of the block gain entry points (openpano_amd/csrc/overlap.hip, blend_sample.hpp, photometric_solve.cc) for
  * tests/test_gpu_gain_blocks.py, built like gain_overlap_ref.c (included below for its image type, interpolate() and
  * sampling rules) with -ffp-contract=off so that every fp64 / fp32 operation is the device's:
  *   gain_block_overlap_ref  op_gain_block_overlap (k_gain_block_overlap): op_gain_overlap's statistics split by block pair,

@@ -1,4 +1,4 @@
-/* gain_overlap_ref.c -- CPU restatement of op_gain_overlap (openpano_amd/csrc/blend.hip: k_gain_overlap) for
+/* gain_overlap_ref.c -- CPU restatement of op_gain_overlap (openpano_amd/csrc/overlap.hip: k_gain_overlap) for
  * tests/test_gpu_gain.py.  Plain C, built by the test with -ffp-contract=off so that every fp64 / fp32 operation is the
  * device's: the canvas -> image map of ConnectedImages::blend with the per-column sin / cos and per-row tan from this
  * host's libm (what the library tabulates), the linear blender's validity rules, interpolate(), and the fixed-point

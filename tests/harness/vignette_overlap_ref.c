@@ -1,4 +1,4 @@
-/* vignette_overlap_ref.c -- CPU restatements of the vignetting entry points (openpano_amd/csrc/blend.hip) for
+/* vignette_overlap_ref.c -- CPU restatements of the vignetting entry points (openpano_amd/csrc/overlap.hip, blend_sample.hpp, photometric_solve.cc) for
  * tests/test_gpu_vignette.py, built like gain_block_overlap_ref.c (included below for the image type, the map and the
  * sampling rules) with -ffp-contract=off so that every fp64 / fp32 operation is the device's:
  *   vignette_overlap_ref   op_vignette_overlap (k_vignette_overlap): per pair, the count and the 30 moments of the grey

@@ -153,7 +153,7 @@ def _checker(h, w, cell):
 
 
 def quantise(canvas):
-    """k_to_u8's expression (csrc/blend.hip): Color::NO (negative) -> 255, v * 255 in fp32, truncated"""
+    """canvas_byte (csrc/internal.hpp): Color::NO (negative) -> 255, v * 255 in fp32, truncated"""
     v = np.where(canvas < 0, np.float32(1), canvas).astype(np.float32)
     return (v * np.float32(255)).astype(np.uint8)
 

@@ -1,4 +1,4 @@
-"""GPU: exposure (gain) compensation -- op_gain_overlap / op_gain_solve / op_blend_gains (csrc/blend.hip).
+"""GPU: exposure (gain) compensation -- op_gain_overlap (csrc/overlap.hip) / op_gain_solve (photometric_solve.cc) / op_blend_gains (blend.hip).
 
 1. the overlap statistics equal a CPU restatement (tests/harness/gain_overlap_ref.c, host libm for the map's trig, like
    the blend's tables) EXACTLY: counts and fixed-point int64 sums, for every projection, both LAZY_READ branches,

@@ -1,4 +1,4 @@
-"""GPU: block gain compensation -- op_gain_block_overlap / op_gain_block_solve / op_blend_block_gains (csrc/blend.hip).
+"""GPU: block gain compensation -- op_gain_block_overlap (csrc/overlap.hip) / op_gain_block_solve (photometric_solve.cc) / op_blend_block_gains (blend.hip).
 
 1. the block statistics equal a CPU restatement (tests/harness/gain_block_overlap_ref.c) EXACTLY: counts and fixed-point
    int64 sums per unit pair, for every projection, both LAZY_READ branches, strides 1 and 3, grids 1 x 1, 3 x 2 and 4 x 4,

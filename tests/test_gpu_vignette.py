@@ -1,4 +1,4 @@
-"""GPU: vignetting compensation -- op_vignette_overlap / op_vignette_solve / op_blend_vignette (csrc/blend.hip).
+"""GPU: vignetting compensation -- op_vignette_overlap (csrc/overlap.hip) / op_vignette_solve (photometric_solve.cc) / op_blend_vignette (blend.hip).
 
 1. the statistics equal a CPU restatement (tests/harness/vignette_overlap_ref.c) EXACTLY: counts and the 30 fixed-point
    int64 moments per pair, for every projection, both LAZY_READ branches, strides 1 and 3, clip 1 and 0.9, pixels covered

@@ -48,7 +48,7 @@ def test_byte_conversions_equal_the_division():
     is the other exact form.  The fp32 multiply by 1.f / 255.f is NOT one (so it must never be used)."""
     b = np.arange(256)
     ref = (b.astype(np.float64) / 255.0).astype(np.float32)
-    assert np.array_equal((b.astype(np.float64) * (1.0 / 255.0)).astype(np.float32), ref)       # csrc/blend.hip: byte_pixel
+    assert np.array_equal((b.astype(np.float64) * (1.0 / 255.0)).astype(np.float32), ref)       # csrc/blend_sample.hpp: byte_pixel
     assert np.array_equal(b.astype(np.float32) / np.float32(255.0), ref)
     bad = b.astype(np.float32) * (np.float32(1.0) / np.float32(255.0))
     assert (bad != ref).sum() == 126

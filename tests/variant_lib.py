@@ -38,7 +38,7 @@ def build_variant(out_dir, stem, flags):
             objs.append(prebuilt)
             continue
         o = os.path.join(str(out_dir), name + ".o")
-        jobs.append(subprocess.Popen(["g++", "-std=c++17", "-O3", "-ffp-contract=off", "-fPIC", "-Wno-psabi", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + CSRC, "-c", src, "-o", o]))
+        jobs.append(subprocess.Popen(["g++", "-std=c++17", "-O3", "-ffp-contract=off", "-fPIC", "-Wno-psabi", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-c", src, "-o", o]))
         objs.append(o)
     assert all(j.wait() == 0 for j in jobs)
     lib = os.path.join(str(out_dir), "libopenpano_hip_variant.so")
