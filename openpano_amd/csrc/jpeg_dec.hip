@@ -1,7 +1,8 @@
 // jpeg_dec.hip -- baseline JPEG files decoded on the device into resident views.
 //
 // Stands in for read_img -> CImg::load -> libjpeg (lib/imgio.cc:67-90, reached from ImageRef::load, stitch/imageref.hh:22-27):
-// SOF0, 8 bits, one interleaved scan, YCbCr at 4:4:4 / 4:2:2 / 4:2:0 or grey, any tables, with or without restart markers.
+// SOF0, 8 bits, one interleaved scan, YCbCr at 4:4:4 / 4:2:2 / 4:2:0 or grey, any tables (tests/test_gpu_jpeg_craft.py holds it
+// to that: tables per component, odd code shapes, every layout of the segments), with or without restart markers.
 // Every byte of a view is what libjpeg's default decode gives (ISLOW IDCT, fancy upsampling, JFIF colour conversion).
 // The host parses headers only (jpeg_dec_parse.hpp); the entropy-coded data goes up as it is.  Six launches per batch,
 // blockIdx.y (or .x where the grid is one workgroup per image) = image:
@@ -230,7 +231,7 @@ __global__ void __launch_bounds__(256) k_jd_coef(const JdImage* __restrict__ img
 	short* out = coef + I.coef_off;
 	uint32_t err = 0;
 	while (c.pos < se) {
-		if (blk >= limit) { if (!last || c.zz) err |= JD_ERR_COUNT; break; }      // behind the last block: the bits that pad the interval to a byte
+		if (blk >= limit) { if (!jd_tail_is_padding(last, c, e)) err |= JD_ERR_COUNT; break; }      // behind the last block: the bits that pad the interval to a byte
 		int idx = 0, val = 0;
 		const uint32_t fl = jd_step(d, e, huff, kinfo, bpm, c, idx, val);
 		err |= fl & 0xFFu;

@@ -123,6 +123,10 @@ JD_HD void jd_run(const uint8_t* d, uint32_t sub_end, uint32_t end, const JdHuff
 	while (c.pos < sub_end) { int idx, val; (void)jd_step(d, end, huff, kinfo, bpm, c, idx, val); }
 }
 
+// Behind an interval's last block (pass C, on the true path) only the bits that pad the interval to a byte may follow: fewer
+// than eight, in the interval's last subsequence, at a block boundary.  A whole byte or more there is a block too many, whatever S is.
+JD_HD bool jd_tail_is_padding(bool last_sub, const JdCur& c, uint32_t end) { return last_sub && c.zz == 0 && end - c.pos < 8; }
+
 // One subsequence in one round of the synchronisation.  Round 0 (pass A) decodes from the subsequence's first bit in state
 // (block 0, position 0), which is the true state for an interval's first subsequence.  A later round (pass B) re-decodes
 // from the predecessor's exit state if that changed in the round before, and marks its own exit as changed when its

@@ -99,7 +99,7 @@ static int model_decode(const unsigned char* f, int64_t size, uint32_t S, Model&
 		if (l == 0) { c.pos = b0; c.k = 0; c.zz = 0; } else c = jd_unpack(A[s - 1]);
 		c.n = 0;
 		while (c.pos < se) {
-			if (blk >= limit) { if (!last || c.zz) err |= JD_ERR_COUNT; break; }
+			if (blk >= limit) { if (!jd_tail_is_padding(last, c, e)) err |= JD_ERR_COUNT; break; }
 			int idx = 0, val = 0;
 			const uint32_t fl = jd_step(d, e, I.huff, I.kinfo, bpm, c, idx, val);
 			err |= fl & 0xFFu;

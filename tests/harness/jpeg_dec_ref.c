@@ -9,6 +9,12 @@
 
 typedef struct {
 	int32_t stuffed, zrl, end63, max_dc_cat, max_ac_cat, max_code_len, intervals, blocks;
+	int32_t max_zrl_chain;            /* the longest run of ZRL symbols in a row */
+	int32_t unpadded, unpadded_last, pad_zero;     /* intervals that end on a byte boundary; whether the last one does; intervals with a 0 among their pad bits */
+	int32_t end_ff;                   /* intervals whose last data byte is FF */
+	int32_t eob_after_dc, full_blocks, run15;      /* blocks of a DC and an EOB; blocks of 63 non-zero ACs; symbols F1..FA */
+	int32_t end63_zrl[4];             /* coefficient 63 written right behind 0, 1, 2, 3 ZRLs */
+	int32_t dc_bound[12], ac_bound[11];            /* per category s: bit 0: -(2^s - 1) seen, 1: -2^(s-1), 2: +2^(s-1), 3: +(2^s - 1) */
 } jpeg_dec_ref_stats_t;
 static jpeg_dec_ref_stats_t g_stats;
 void jpeg_dec_ref_stats(jpeg_dec_ref_stats_t* s) { *s = g_stats; }
@@ -158,26 +164,36 @@ static void trace_boundary(trace_t* T, long pos, int k, int zz) {
 	}
 }
 
+static void note_bound(int32_t* seen, int s, int v) {
+	if (v == -((1 << s) - 1)) seen[s] |= 1;
+	if (v == -(1 << (s - 1))) seen[s] |= 2;
+	if (v == 1 << (s - 1)) seen[s] |= 4;
+	if (v == (1 << s) - 1) seen[s] |= 8;
+}
+
 /* one block: coefficients in natural order, the DC as the value (pred updated).  0, or -1 on broken data */
 static int decode_block(bits_t* b, const huff_t* dc, const huff_t* ac, int* pred, int16_t* coef, trace_t* T, int kblk) {
 	int bad = 0;
 	int s = get_symbol(b, dc);
 	if (s < 0 || s > 11) return -1;
 	if (s > g_stats.max_dc_cat) g_stats.max_dc_cat = s;
-	*pred += get_value(b, s, &bad);
+	const int diff = get_value(b, s, &bad);
 	if (bad) return -1;
+	if (s) note_bound(g_stats.dc_bound, s, diff);
+	*pred += diff;
 	coef[0] = (int16_t)*pred;
 	trace_boundary(T, b->pos, kblk, 1);
-	int k = 1;
+	int k = 1, chain = 0, nonzero = 0;
 	while (k < 64) {
 		const int rs = get_symbol(b, ac);
 		if (rs < 0) return -1;
 		const int r = rs >> 4;
 		s = rs & 15;
 		if (s == 0) {
-			if (r != 15) { k = 64; break; }      /* EOB */
+			if (r != 15) { if (k == 1) ++g_stats.eob_after_dc; k = 64; break; }      /* EOB */
 			if (k + 16 > 63) return -1;
 			k += 16; ++g_stats.zrl;
+			if (++chain > g_stats.max_zrl_chain) g_stats.max_zrl_chain = chain;
 			trace_boundary(T, b->pos, kblk, k);
 			continue;
 		}
@@ -187,7 +203,11 @@ static int decode_block(bits_t* b, const huff_t* dc, const huff_t* ac, int* pred
 		if (k > 63) return -1;
 		coef[ZZ[k]] = (int16_t)get_value(b, s, &bad);
 		if (bad) return -1;
-		if (k == 63) ++g_stats.end63;
+		note_bound(g_stats.ac_bound, s, coef[ZZ[k]]);
+		if (r == 15) ++g_stats.run15;
+		if (k == 63) { ++g_stats.end63; if (chain < 4) ++g_stats.end63_zrl[chain]; }
+		if (++nonzero == 63) ++g_stats.full_blocks;
+		chain = 0;
 		++k;
 		if (k < 64) trace_boundary(T, b->pos, kblk, k);
 	}
@@ -284,6 +304,13 @@ static long run(const uint8_t* f, long size, uint8_t* rgb, long cap, int* h, int
 				const long bx = (m % mcuw) * hsc + sub % hsc, by = (m / mcuw) * vsc + sub / hsc;
 				for (int i = 0; i < 64; ++i) plane[c][(by * 8 + i / 8) * pw[c] + bx * 8 + i % 8] = (uint8_t)clamp255(ws[i] + 128);
 			}
+		}
+		if (!ret) {      /* how the interval ends: its pad bits and its last byte */
+			int zero = 0;
+			if (b.pos == b.end) { ++g_stats.unpadded; g_stats.unpadded_last = j + 1 == nint; }
+			for (long p = b.pos; p < b.end; ++p) if (!((data[p >> 3] >> (7 - (p & 7))) & 1)) zero = 1;
+			g_stats.pad_zero += zero;
+			if (iv[j + 1] > iv[j] && data[iv[j + 1] - 1] == 0xFF) ++g_stats.end_ff;
 		}
 		/* what is left of the interval pads it to a byte: the last subsequence ends here */
 		if (!ret && tracing) { if (T.sub_end <= T.iv_end) { T.sub_end = T.iv_end; trace_boundary(&T, b.end, 0, 0); } }

@@ -35,10 +35,12 @@ def sampling_of(name):
 
 class Stats(C.Structure):
     """jpeg_dec_ref_stats_t of jpeg_dec_ref.c"""
-    _fields_ = [(k, C.c_int32) for k in ("stuffed", "zrl", "end63", "max_dc_cat", "max_ac_cat", "max_code_len", "intervals", "blocks")]
+    _fields_ = [(k, C.c_int32) for k in ("stuffed", "zrl", "end63", "max_dc_cat", "max_ac_cat", "max_code_len", "intervals", "blocks",
+                                         "max_zrl_chain", "unpadded", "unpadded_last", "pad_zero", "end_ff", "eob_after_dc", "full_blocks", "run15")] + \
+               [("end63_zrl", C.c_int32 * 4), ("dc_bound", C.c_int32 * 12), ("ac_bound", C.c_int32 * 11)]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+        return {k: getattr(self, k) if t is C.c_int32 else list(getattr(self, k)) for k, t in self._fields_}
 
 
 def build_ref(tmpdir):
