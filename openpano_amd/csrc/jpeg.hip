@@ -5,15 +5,15 @@
 // MCUs.  A restart interval is byte-aligned and starts its DC prediction at 0, so intervals are independent.  Two kernels:
 //   k_jpeg_interval  one workgroup per restart interval: quantise the canvas (canvas_byte), RGB -> YCbCr,
 //                    4:2:0 chroma averaging, IJG slow-integer forward DCT (rows, then columns), quantisation, zigzag -- all in
-//                    LDS; one thread per block counts its bits, a prefix sum places them, the codes are ORed into an LDS bit
-//                    image, a second prefix sum (of 0xFF bytes) places the stuffed bytes in the interval's slot;
-//   k_jpeg_pack      exclusive scan of the slot sizes, every interval copied to its place behind the header, RSTn between
-//                    them, EOI at the end.
+//                    LDS; one thread per block counts its bits, a prefix sum (wg_scan_inclusive) places them, MsbWriter ORs the codes
+//                    into an LDS bit image, a second prefix sum (of 0xFF bytes) places the stuffed bytes in the interval's slot;
+//   k_jpeg_pack      exclusive scan of the slot sizes (wg_slot_offset), every interval copied to its place behind the header,
+//                    RSTn between them, EOI at the end.  (These helpers, sample_byte and the file handle: codec_shared.hpp.)
 // The header (SOI .. SOS, 623 bytes) is written by the host.  All arithmetic after the byte quantisation is integer and the
 // only atomics are integer OR / add on LDS, so the file is a function of the pixels alone; tests/harness/jpeg_ref.c is the same
 // encoder written serially, its files equal libjpeg's byte for byte, and the GPU tests require the device's to equal its.
-#include "internal.hpp"
-#include <cstring>
+#include "codec_shared.hpp"
+#include "jpeg_tables.hpp"
 
 // MCUs per restart interval (8 x 8 pixels at 4:4:4, 16 x 16 at 4:2:0); tests/harness/jpeg_ref.c has the same knobs
 #ifndef OP_JPEG_RI_444
@@ -27,32 +27,19 @@
 #define JPEG_ZS 66                  // shorts per block of zigzagged coefficients: 33 words, one bank apart per thread
 static_assert(OP_JPEG_RI_444 >= 1 && OP_JPEG_RI_444 * 3 <= 256 && OP_JPEG_RI_420 >= 1 && OP_JPEG_RI_420 * 6 <= 256, "one thread codes one block");
 
-struct op_jpeg {
-	std::vector<unsigned char> bytes;
-};
+struct op_jpeg : EncodedFile {};
 
 namespace {
 
-__constant__ unsigned char c_k1[64] = {
-	16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-	18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-__constant__ unsigned char c_k2[64] = {
-	17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-	99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-// natural index -> zigzag position
-__constant__ unsigned char c_zz_pos[64] = {
-	0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53,
-	10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
-// zigzag position -> natural index (the header's DQT segments)
-const unsigned char h_zz_nat[64] = {
-	0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-	35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-const unsigned char h_k1[64] = {
-	16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-	18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-const unsigned char h_k2[64] = {
-	17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-	99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// the quantiser bases and the zigzag order (the header's DQT segments) are jpeg_tables.hpp's, shared with the decoder
+__constant__ unsigned char c_k1[64] = JPEG_K1_LUMA, c_k2[64] = JPEG_K2_CHROMA;
+const unsigned char h_k1[64] = JPEG_K1_LUMA, h_k2[64] = JPEG_K2_CHROMA, h_zigzag[64] = JPEG_ZZ_NAT;
+// natural index -> zigzag position: the inverse of JPEG_ZZ_NAT
+#define JPEG_ZZ_POS {0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, \
+	10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63}
+__constant__ unsigned char c_zz_pos[64] = JPEG_ZZ_POS;
+static_assert([] { constexpr unsigned char pos[64] = JPEG_ZZ_POS, nat[64] = JPEG_ZZ_NAT; for (int k = 0; k < 64; ++k) if (pos[nat[k]] != k) return false; return true; }(),
+	"c_zz_pos must send every natural index to its place in the one zigzag order");
 
 // ITU T.81 Annex K.3: code counts per length 1..16 and the symbols in code order; index 0 luma, 1 chroma
 #define JPEG_DC_COUNTS {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}}
@@ -83,13 +70,10 @@ __host__ __device__ inline int jpeg_q(int base, int quality) {
 	return v < 1 ? 1 : v > 255 ? 255 : v;
 }
 
-__device__ __forceinline__ int jpx(const float* p, long long i) { return (int)canvas_byte(p[i]); }
-__device__ __forceinline__ int jpx(const unsigned char* p, long long i) { return (int)p[i]; }
-
 template <typename T>
 __device__ __forceinline__ void load_ycc(const T* __restrict__ src, int w, int y, int x, int& Y, int& Cb, int& Cr) {
 	const long long i = 3 * ((long long)y * w + x);
-	const int R = jpx(src, i), G = jpx(src, i + 1), B = jpx(src, i + 2);
+	const int R = sample_byte(src, i), G = sample_byte(src, i + 1), B = sample_byte(src, i + 2);
 	Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
 	Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
 	Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
@@ -129,38 +113,30 @@ __device__ __forceinline__ uint32_t huff_entry(const unsigned char* counts, int 
 	return 0;
 }
 
-// MSB-first bit writer into zeroed LDS words (word = 4 file bytes, big-endian); neighbours share words, so every store is an OR
-struct JBitW { uint32_t* w; unsigned long long acc; int n; };
-__device__ __forceinline__ void jw_init(JBitW& b, uint32_t* base, uint32_t bitoff) { b.w = base + (bitoff >> 5); b.acc = 0; b.n = (int)(bitoff & 31); }
-__device__ __forceinline__ void jw_put(JBitW& b, uint32_t v, int nb) {      // nb <= 27
-	b.acc = b.acc << nb | v; b.n += nb;
-	if (b.n >= 32) { b.n -= 32; atomicOr(b.w++, (uint32_t)(b.acc >> b.n)); b.acc &= (1ull << b.n) - 1; }
-}
-__device__ __forceinline__ void jw_flush(JBitW& b) { if (b.n > 0) atomicOr(b.w, (uint32_t)(b.acc << (32 - b.n))); }
 __device__ __forceinline__ int bit_length(int v) { return 32 - __clz(v); }      // v >= 0
 
-// Huffman entry = code << 5 | length.  EMIT = false: only the block's length in bits is returned.
+// Huffman entry = code << 5 | length.  EMIT = false: only the block's length in bits is returned.  No put exceeds 16 + 11 bits.
 template <bool EMIT>
-__device__ __forceinline__ uint32_t code_block(const short* zz, int pred, const uint32_t* hdc, const uint32_t* hac, JBitW& bw) {
+__device__ __forceinline__ uint32_t code_block(const short* zz, int pred, const uint32_t* hdc, const uint32_t* hac, MsbWriter& bw) {
 	uint32_t bits = 0;
 	{
 		const int d = (int)zz[0] - pred, cat = bit_length(d < 0 ? -d : d);
 		const uint32_t e = hdc[cat], len = e & 31;
 		bits += len + cat;
-		if (EMIT) jw_put(bw, (e >> 5) << cat | ((uint32_t)(d > 0 ? d : d - 1) & ((1u << cat) - 1)), (int)len + cat);
+		if (EMIT) bw.put((e >> 5) << cat | ((uint32_t)(d > 0 ? d : d - 1) & ((1u << cat) - 1)), (int)len + cat);
 	}
 	int run = 0;
 	for (int k = 1; k < 64; ++k) {
 		const int v = zz[k];
 		if (!v) { ++run; continue; }
-		while (run >= 16) { const uint32_t e = hac[0xF0]; bits += e & 31; if (EMIT) jw_put(bw, e >> 5, (int)(e & 31)); run -= 16; }
+		while (run >= 16) { const uint32_t e = hac[0xF0]; bits += e & 31; if (EMIT) bw.put(e >> 5, (int)(e & 31)); run -= 16; }
 		const int cat = bit_length(v < 0 ? -v : v);
 		const uint32_t e = hac[run << 4 | cat], len = e & 31;
 		bits += len + cat;
-		if (EMIT) jw_put(bw, (e >> 5) << cat | ((uint32_t)(v > 0 ? v : v - 1) & ((1u << cat) - 1)), (int)len + cat);
+		if (EMIT) bw.put((e >> 5) << cat | ((uint32_t)(v > 0 ? v : v - 1) & ((1u << cat) - 1)), (int)len + cat);
 		run = 0;
 	}
-	if (run) { const uint32_t e = hac[0]; bits += e & 31; if (EMIT) jw_put(bw, e >> 5, (int)(e & 31)); }
+	if (run) { const uint32_t e = hac[0]; bits += e & 31; if (EMIT) bw.put(e >> 5, (int)(e & 31)); }
 	return bits;
 }
 
@@ -180,16 +156,6 @@ struct JpegLds {
 	unsigned char dummy[NB];
 	short mcu_y[JpegGeom<MODE>::RI], mcu_x[JpegGeom<MODE>::RI];
 };
-
-// inclusive prefix sum of S.scan[0..256) by 256 threads
-__device__ __forceinline__ void scan256(uint32_t* a, int t) {
-	for (int off = 1; off < 256; off <<= 1) {
-		const uint32_t v = t >= off ? a[t - off] : 0;
-		__syncthreads();
-		a[t] += v;
-		__syncthreads();
-	}
-}
 
 // slots: nint x SLOT bytes, SLOT = 2 * NB * 208 (every block at its worst, every byte stuffed); sizes: bytes used per slot
 template <typename T, int MODE>
@@ -294,7 +260,7 @@ __global__ void __launch_bounds__(256) k_jpeg_interval(const T* __restrict__ src
 	const int comp = b % BPM, tq = comp >= (MODE == OP_JPEG_420 ? 4 : 1) ? 1 : 0;
 	int pred = 0;
 	uint32_t mybits = 0;
-	JBitW bw = {nullptr, 0, 0};
+	MsbWriter bw = {nullptr, 0, 0};
 	if (coding && !dummy) {
 		// the previous block of the same component inside the interval; a dummy Y block repeats the DC before it, so it is skipped
 		if (MODE == OP_JPEG_444 || comp >= 4) { if (b >= BPM) pred = S.zz[(b - BPM) * JPEG_ZS]; }
@@ -309,13 +275,13 @@ __global__ void __launch_bounds__(256) k_jpeg_interval(const T* __restrict__ src
 	} else if (dummy) mybits = (S.hdc[0][0] & 31) + (S.hac[0][0] & 31);      // DC difference 0, end of block
 	S.scan[t] = mybits;
 	__syncthreads();
-	scan256(S.scan, t);
+	wg_scan_inclusive<256>(S.scan, t);
 	const uint32_t total = S.scan[255];
 	if (coding) {
-		jw_init(bw, S.u.bits, S.scan[t] - mybits);
-		if (dummy) { jw_put(bw, S.hdc[0][0] >> 5, (int)(S.hdc[0][0] & 31)); jw_put(bw, S.hac[0][0] >> 5, (int)(S.hac[0][0] & 31)); }
+		bw.init(S.u.bits, S.scan[t] - mybits);
+		if (dummy) { bw.put(S.hdc[0][0] >> 5, (int)(S.hdc[0][0] & 31)); bw.put(S.hac[0][0] >> 5, (int)(S.hac[0][0] & 31)); }
 		else code_block<true>(S.zz + b * JPEG_ZS, pred, S.hdc[tq], S.hac[tq], bw);
-		jw_flush(bw);
+		bw.flush();
 	}
 	const int pad = (int)(-total & 7);
 	if (t == 0 && pad) atomicOr(&S.u.bits[total >> 5], ((1u << pad) - 1) << (32 - (int)(total & 31) - pad));      // 1-bits up to the byte
@@ -329,7 +295,7 @@ __global__ void __launch_bounds__(256) k_jpeg_interval(const T* __restrict__ src
 	__syncthreads();
 	S.scan[t] = ff;
 	__syncthreads();
-	scan256(S.scan, t);
+	wg_scan_inclusive<256>(S.scan, t);
 	unsigned char* slot = slots + (long long)blockIdx.x * (2 * NB * JPEG_BLOCK_BYTES);
 	uint32_t o = i0 + S.scan[t] - ff;
 	for (uint32_t i = i0; i < i1; ++i) {
@@ -346,12 +312,7 @@ __global__ void __launch_bounds__(256) k_jpeg_pack(const unsigned char* __restri
 	__shared__ unsigned long long offs;
 	const int t = threadIdx.x, iv = blockIdx.x;
 	if (t == 0) offs = 0;
-	__syncthreads();
-	// exclusive scan of the interval sizes (each followed by a 2-byte marker): every workgroup sums the intervals before its own
-	unsigned long long part = 0;
-	for (int k = t; k < iv; k += 256) part += 2ull + sizes[k];
-	if (part) atomicAdd(&offs, part);
-	__syncthreads();
+	wg_slot_offset(offs, sizes, iv, 2);      // each interval is followed by a 2-byte marker
 	const uint32_t size = sizes[iv];
 	unsigned char* o = out + offs;
 	const unsigned char* slot = slots + (long long)iv * slot_bytes;
@@ -370,7 +331,7 @@ std::vector<unsigned char> jpeg_header(int h, int w, int quality, int subsamplin
 	std::vector<unsigned char> o = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
 	for (int t = 0; t < 2; ++t) {
 		o.push_back(0xFF); o.push_back(0xDB); put16(o, 67); o.push_back((unsigned char)t);
-		for (int k = 0; k < 64; ++k) o.push_back((unsigned char)jpeg_q((t ? h_k2 : h_k1)[h_zz_nat[k]], quality));
+		for (int k = 0; k < 64; ++k) o.push_back((unsigned char)jpeg_q((t ? h_k2 : h_k1)[h_zigzag[k]], quality));
 	}
 	o.push_back(0xFF); o.push_back(0xC0); put16(o, 17); o.push_back(8); put16(o, h); put16(o, w); o.push_back(3);
 	for (int c = 0; c < 3; ++c) { o.push_back((unsigned char)(c + 1)); o.push_back(c == 0 && subsampling == OP_JPEG_420 ? 0x22 : 0x11); o.push_back(c ? 1 : 0); }
@@ -421,18 +382,9 @@ int encode_device(op_ctx* ctx, CallBlocks& own, const void* src, bool is_float, 
 	{ ProfScope ps(ctx, "jpeg pack");
 	  hipLaunchKernelGGL(k_jpeg_pack, dim3(nint), dim3(256), 0, st, slots, sizes, slot_bytes, nint, obuf, total);
 	  HIPCHK(hipGetLastError()); }
-	unsigned long long n = 0;
-	HIPCHK(hipMemcpyAsync(&n, total, sizeof(n), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	if (n < 3 || n > cap) OP_FAIL(OP_ERR_HIP, std::string(who) + ": the device reported an impossible file size");
-	std::unique_ptr<op_jpeg, void (*)(op_jpeg*)> jpg(new op_jpeg, op_jpeg_free);
+	std::unique_ptr<op_jpeg> jpg(new op_jpeg);
 	jpg->bytes = jpeg_header(h, w, quality, subsampling);
-	const size_t head = jpg->bytes.size();
-	jpg->bytes.resize(head + (size_t)n);
-	{ ProfScope ps(ctx, "jpeg D2H");
-	  HIPCHK(hipMemcpyAsync(jpg->bytes.data() + head, obuf, (size_t)n, hipMemcpyDeviceToHost, st)); }
-	HIPCHK(own.finish());
-	resolve_profile(ctx);
+	if (const int r = encoded_fetch(ctx, own, obuf, total, 3, cap, *jpg, "jpeg D2H", who)) return r;      // at least one byte and EOI
 	*out = jpg.release();
 	return OP_OK;
 }
@@ -455,22 +407,14 @@ int op_jpeg_encode_u8(op_ctx* ctx, const unsigned char* rgb_host, int h, int w, 
 	if (!ctx || !rgb_host || !out) OP_FAIL(OP_ERR_INVALID, "op_jpeg_encode_u8: bad argument");
 	if (const int r = check_args(h, w, quality, subsampling, "op_jpeg_encode_u8")) return r;
 	HIPCHK(hipSetDevice(ctx->device));
-	const size_t n = (size_t)h * w * 3;
 	CallBlocks own({ctx->stream});
 	unsigned char* d = nullptr;
-	HIPCHK(own.alloc(&d, n));
-	HIPCHK(hipMemcpyAsync(d, rgb_host, n, hipMemcpyHostToDevice, ctx->stream));
+	if (const int r = stage_rgb_u8(ctx, own, rgb_host, h, w, &d)) return r;
 	return encode_device(ctx, own, d, false, h, w, quality, subsampling, out, "op_jpeg_encode_u8");
 }
 
-int64_t op_jpeg_size(const op_jpeg* p) { return p ? (int64_t)p->bytes.size() : 0; }
-
-int op_jpeg_copy(op_ctx* ctx, const op_jpeg* p, unsigned char* host) {
-	(void)ctx;
-	if (!p || !host) OP_FAIL(OP_ERR_INVALID, "op_jpeg_copy: bad argument");
-	memcpy(host, p->bytes.data(), p->bytes.size());
-	return OP_OK;
-}
+int64_t op_jpeg_size(const op_jpeg* p) { return encoded_size(p); }
+int op_jpeg_copy(op_ctx*, const op_jpeg* p, unsigned char* host) { return encoded_copy("op_jpeg_copy", p, host); }
 
 void op_jpeg_free(op_jpeg* p) { delete p; }
 

@@ -6,7 +6,7 @@
 // Every byte of a view is what libjpeg's default decode gives (ISLOW IDCT, fancy upsampling, JFIF colour conversion).
 // The host parses headers only (jpeg_dec_parse.hpp); the entropy-coded data goes up as it is.  Six launches per batch,
 // blockIdx.y (or .x where the grid is one workgroup per image) = image:
-//   k_jd_scan   one workgroup per image: flags FF 00 and FF D0..D7, a prefix sum compacts the data and yields the table of
+//   k_jd_scan   one workgroup per image: flags FF 00 and FF D0..D7, a prefix sum (wg_scan_inclusive) compacts the data and yields the table of
 //               restart intervals and the number of subsequences of each; any other marker sets the error word;
 //   k_jd_sync   one workgroup per image (its restart intervals dealt over up to 64): passes A and B of the self-synchronising Huffman decode (Weissenberger & Schmidt)
 //               over subsequences of S bits, rounds separated by barriers, then a prefix sum of the blocks each completes;
@@ -16,10 +16,9 @@
 //   k_jd_rgb    a thread per output pixel: chroma upsampling and YCbCr -> RGB, bytes written into the view.
 // The symbol step, the state and the convergence rule are jpeg_dec_core.hpp's, shared with the host model and the serial
 // restatement's checks (tests/harness).  All arithmetic is integer: a view is a function of the file alone.
-#include "internal.hpp"
+#include "codec_shared.hpp"
 #include "jpeg_dec_core.hpp"
 #include "jpeg_dec_parse.hpp"
-#include <cstring>
 
 static_assert(JD_OK == OP_OK && JD_INVALID == OP_ERR_INVALID && JD_UNSUPPORTED == OP_ERR_UNSUPPORTED, "the parser returns the C-ABI's codes");
 static_assert(JD_S444 == OP_JPEG_444 && JD_S420 == OP_JPEG_420 && JD_S422 == OP_JPEG_422 && JD_GREY == OP_JPEG_GREY, "the parser returns the C-ABI's samplings");
@@ -29,17 +28,7 @@ namespace {
 #define JD_WG 1024         // threads of the one-workgroup-per-image kernels
 #define JD_RUN 8           // bytes a thread of k_jd_scan owns per tile
 
-__constant__ unsigned char c_jd_zz_nat[64] = JD_ZZ_NAT;
-
-// inclusive prefix sum of a[0..JD_WG) by JD_WG threads
-__device__ __forceinline__ void scan_wg(uint32_t* a, int t) {
-	for (int off = 1; off < JD_WG; off <<= 1) {
-		const uint32_t v = t >= off ? a[t - off] : 0;
-		__syncthreads();
-		a[t] += v;
-		__syncthreads();
-	}
-}
+__constant__ unsigned char c_jd_zz_nat[64] = JPEG_ZZ_NAT;
 
 // the interval that holds subsequence s: the largest j with subfirst[j] <= s (subfirst[0] = 0, subfirst[nint] = nsub > s)
 __device__ __forceinline__ uint32_t find_interval(const uint32_t* __restrict__ subfirst, uint32_t nint, uint32_t s) {
@@ -90,8 +79,8 @@ __global__ void __launch_bounds__(JD_WG) k_jd_scan(const JdImage* __restrict__ i
 		const uint32_t nk = __popc(keep), nm = __popc(mark);
 		sk[t] = nk; sm[t] = nm;
 		__syncthreads();
-		scan_wg(sk, t);
-		scan_wg(sm, t);
+		wg_scan_inclusive<JD_WG>(sk, t);
+		wg_scan_inclusive<JD_WG>(sm, t);
 		uint32_t ok = basek + sk[t] - nk, om = basem + sm[t] - nm;
 #pragma unroll
 		for (int j = 0; j < JD_RUN; ++j) {
@@ -119,7 +108,7 @@ __global__ void __launch_bounds__(JD_WG) k_jd_scan(const JdImage* __restrict__ i
 		maxl = max(maxl, ns);
 		sk[t] = ns;
 		__syncthreads();
-		scan_wg(sk, t);
+		wg_scan_inclusive<JD_WG>(sk, t);
 		if (j < nint) sf[j] = base + sk[t] - ns;
 		base += sk[JD_WG - 1];
 		__syncthreads();
@@ -189,7 +178,7 @@ __global__ void __launch_bounds__(JD_WG) k_jd_sync(const JdImage* __restrict__ i
 		const uint32_t c = s < s1 ? jd_count(F[s]) : 0;
 		sc[t] = c;
 		__syncthreads();
-		scan_wg(sc, t);
+		wg_scan_inclusive<JD_WG>(sc, t);
 		if (s < s1) pex[I.sub_off + s] = base + sc[t] - c;
 		base += sc[JD_WG - 1];
 		__syncthreads();

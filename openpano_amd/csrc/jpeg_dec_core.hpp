@@ -1,9 +1,10 @@
 // jpeg_dec_core.hpp -- the per-symbol step, the state and the pass-B convergence rule of the self-synchronising baseline
 // JPEG Huffman decode.  One text for the kernels of jpeg_dec.hip, for the host model that
 // tests/test_jpeg_dec_cpu.py runs (tests/harness/jpeg_dec_fuzz.cc) and for the sanitizer program built from the same file.
-// Plain C++ with no dependency but <stdint.h>.
+// Plain C++ with no dependency but <stdint.h> and the macros of jpeg_tables.hpp.
 #pragma once
 #include <stdint.h>
+#include "jpeg_tables.hpp"
 
 #if defined(__HIPCC__)
 #define JD_HD __host__ __device__ __forceinline__
@@ -27,9 +28,7 @@ enum { JD_ERR_MARKER = 1,      // a marker other than RSTn in the entropy-coded 
 // result bits of jd_step that are no errors
 enum { JD_BLOCK_DONE = 1 << 8, JD_COEF = 1 << 9, JD_ZRL = 1 << 10, JD_EOB = 1 << 11 };
 
-// zigzag position -> natural index
-#define JD_ZZ_NAT {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, \
-	35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
+#define JD_ZZ_NAT JPEG_ZZ_NAT      // zigzag position -> natural index: the encoder's table (jpeg_tables.hpp)
 
 // One Huffman table as a length-indexed lookup.  The canonical codes of length L, left-justified in 16 bits, fill
 // [lim[L - 1], lim[L]); off[L] + (the L-bit code) is the symbol's place in vals.

@@ -2,19 +2,18 @@
 //
 // Stands in for write_rgb -> write_png -> lodepng::encode (lib/imgio.cc:25-41,98-113), the largest single cost of a whole
 // run of the reference's CLI.  8-bit RGB, colour type 2, no interlace: signature, IHDR, IDAT chunks, IEND.  Three kernels:
-//   k_png_filter   one workgroup per scanline: quantise (canvas_byte) and pick the PNG filter type with
+//   k_png_filter   one workgroup per scanline: quantise (sample_byte) and pick the PNG filter type with
 //                  the smallest sum of |residual as a signed byte|, ties to the lowest type; writes the filtered stream F;
 //   k_png_deflate  one workgroup per PNG_SEG bytes of F: hash candidates, a greedy parse of 256 sub-blocks (one per thread),
-//                  dynamic Huffman tables, bits packed at offsets from a prefix sum; or a stored block when that is not larger.
+//                  dynamic Huffman tables, bits packed (LsbWriter) at offsets from a prefix sum (wg_scan_inclusive); or a stored block when that is not larger.
 //                  Every segment is a byte-aligned piece of ONE deflate stream (closed by an empty stored block; the last one
 //                  carries BFINAL) and becomes its own IDAT chunk, so no CRC has to be combined across segments;
-//   k_png_pack     exclusive scan of the sizes, every piece copied to its place with its chunk length / type / CRC-32; the
+//   k_png_pack     exclusive scan of the sizes (wg_slot_offset), every piece copied to its place with its chunk length / type / CRC-32; the
 //                  zlib header and the Adler-32 (combined from the segments' partial sums) are IDAT chunks of their own.
 // Every choice is fixed by position and value, never by lane or arrival order (LDS atomics used: add, max, or, xor on
 // integers -- all commutative), so the file is a function of the pixels alone; tests/harness/png_ref.c is the same
-// algorithm written serially and the GPU tests require equal bytes.
-#include "internal.hpp"
-#include <cstring>
+// algorithm written serially and the GPU tests require equal bytes.  The named helpers and the file handle: codec_shared.hpp.
+#include "codec_shared.hpp"
 
 #define PNG_SEG 61440        // bytes of filtered stream per segment = 256 sub-blocks; a multiple of 3 (2 SEG + 1 is a possible length)
 #define PNG_SUB 240          // bytes one thread parses; a match never crosses a sub-block's end
@@ -40,15 +39,11 @@ static_assert(OP_PNG_LIT_MAXBITS >= 9 && OP_PNG_LIT_MAXBITS <= 15, "286 codes ne
 static_assert(OP_PNG_DIST_MAXBITS >= 5 && OP_PNG_DIST_MAXBITS <= 15, "30 codes need 5 bits; deflate allows 15");
 static_assert(OP_PNG_CL_MAXBITS >= 5 && OP_PNG_CL_MAXBITS <= 7, "19 codes need 5 bits; a code-length code length is a 3-bit field");
 
-struct op_png {
-	std::vector<unsigned char> bytes;
-};
+struct op_png : EncodedFile {};
 
 namespace {
 
 // ------------------------------------------------ filter ------------------------------------------------
-__device__ __forceinline__ int px(const float* p, long long i) { return (int)canvas_byte(p[i]); }
-__device__ __forceinline__ int px(const unsigned char* p, long long i) { return (int)p[i]; }
 __device__ __forceinline__ int paeth(int a, int b, int c) {
 	const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
 	return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
@@ -66,7 +61,7 @@ __global__ void __launch_bounds__(256) k_png_filter(const T* __restrict__ src, i
 	__syncthreads();
 	unsigned int s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
 	for (long long x = t; x < R; x += 256) {
-		const int v = px(cur, x), a = x >= 3 ? px(cur, x - 3) : 0, b = up ? px(up, x) : 0, c = (up && x >= 3) ? px(up, x - 3) : 0;
+		const int v = sample_byte(cur, x), a = x >= 3 ? sample_byte(cur, x - 3) : 0, b = up ? sample_byte(up, x) : 0, c = (up && x >= 3) ? sample_byte(up, x - 3) : 0;
 		s0 += sabs(v); s1 += sabs(v - a); s2 += sabs(v - b); s3 += sabs(v - ((a + b) >> 1)); s4 += sabs(v - paeth(a, b, c));
 	}
 	atomicAdd(&sum[0], s0); atomicAdd(&sum[1], s1); atomicAdd(&sum[2], s2); atomicAdd(&sum[3], s3); atomicAdd(&sum[4], s4);
@@ -76,7 +71,7 @@ __global__ void __launch_bounds__(256) k_png_filter(const T* __restrict__ src, i
 	unsigned char* o = F + (long long)y * (R + 1);
 	if (t == 0) o[0] = (unsigned char)best;
 	for (long long x = t; x < R; x += 256) {
-		const int v = px(cur, x), a = x >= 3 ? px(cur, x - 3) : 0, b = up ? px(up, x) : 0, c = (up && x >= 3) ? px(up, x - 3) : 0;
+		const int v = sample_byte(cur, x), a = x >= 3 ? sample_byte(cur, x - 3) : 0, b = up ? sample_byte(up, x) : 0, c = (up && x >= 3) ? sample_byte(up, x - 3) : 0;
 		const int pred = best == 0 ? 0 : best == 1 ? a : best == 2 ? b : best == 3 ? ((a + b) >> 1) : paeth(a, b, c);
 		o[1 + x] = (unsigned char)(v - pred);
 	}
@@ -118,15 +113,6 @@ __device__ __forceinline__ void dist_code(int dist, int& code, int& ebits, int& 
 	if (d < 4) { code = d; ebits = 0; eval = 0; }
 	else { const int e = 30 - __clz(d); code = 2 * (e + 1) + ((d >> e) & 1); ebits = e; eval = d & ((1 << e) - 1); }
 }
-
-// LSB-first bit writer into zeroed LDS words; neighbours share words, so every store is an OR
-struct BitW { uint32_t* w; unsigned long long acc; int n; };
-__device__ __forceinline__ void bw_init(BitW& b, uint32_t* base, uint32_t bitoff) { b.w = base + (bitoff >> 5); b.acc = 0; b.n = (int)(bitoff & 31); }
-__device__ __forceinline__ void bw_put(BitW& b, uint32_t v, int nb) {
-	b.acc |= (unsigned long long)v << b.n; b.n += nb;
-	if (b.n >= 32) { atomicOr(b.w++, (uint32_t)b.acc); b.acc >>= 32; b.n -= 32; }
-}
-__device__ __forceinline__ void bw_flush(BitW& b) { if (b.n > 0) atomicOr(b.w, (uint32_t)b.acc); }
 
 // Code lengths (limit maxbits) and canonical codes, bit-reversed for the LSB-first stream, of n symbol counts.  Called by the
 // whole workgroup; every table is in LDS.  Rank by (count, symbol), Moffat-Katajainen in-place lengths, Kraft fix-up,
@@ -312,12 +298,7 @@ __global__ void __launch_bounds__(256) k_png_deflate(const unsigned char* __rest
 	}
 	S.bitoff[t] = mybits;
 	__syncthreads();
-	for (int off = 1; off < 256; off <<= 1) {
-		const uint32_t v = t >= off ? S.bitoff[t - off] : 0;
-		__syncthreads();
-		S.bitoff[t] += v;
-		__syncthreads();
-	}
+	wg_scan_inclusive<256>(S.bitoff, t);
 	if (t == 0) {
 		int hclen = 19;
 		while (hclen > 4 && !S.cllens[c_cl_order[hclen - 1]]) --hclen;
@@ -343,39 +324,39 @@ __global__ void __launch_bounds__(256) k_png_deflate(const unsigned char* __rest
 		const int nwords = (int)((S.size + 3) / 4);
 		for (int k = t; k < nwords; k += 256) S.u.outw[k] = 0;
 		__syncthreads();
-		BitW bw;
+		LsbWriter bw;      // codec_shared.hpp; no put is longer than 16 bits
 		if (t == 0) {
-			bw_init(bw, S.u.outw, 0);
-			bw_put(bw, last ? 1 : 0, 1); bw_put(bw, 2, 2);
-			bw_put(bw, (uint32_t)(S.hlit - 257), 5); bw_put(bw, (uint32_t)(S.hdist - 1), 5); bw_put(bw, (uint32_t)(S.hclen - 4), 4);
-			for (int k = 0; k < S.hclen; ++k) bw_put(bw, S.cllens[c_cl_order[k]], 3);
+			bw.init(S.u.outw, 0);
+			bw.put(last ? 1 : 0, 1); bw.put(2, 2);
+			bw.put((uint32_t)(S.hlit - 257), 5); bw.put((uint32_t)(S.hdist - 1), 5); bw.put((uint32_t)(S.hclen - 4), 4);
+			for (int k = 0; k < S.hclen; ++k) bw.put(S.cllens[c_cl_order[k]], 3);
 			for (int k = 0; k < S.ncl; ++k) {
 				const int c = S.cls[k];
-				bw_put(bw, S.clcodes[c], S.cllens[c]);
-				if (c == 16) bw_put(bw, S.clx[k], 2); else if (c == 17) bw_put(bw, S.clx[k], 3); else if (c == 18) bw_put(bw, S.clx[k], 7);
+				bw.put(S.clcodes[c], S.cllens[c]);
+				if (c == 16) bw.put(S.clx[k], 2); else if (c == 17) bw.put(S.clx[k], 3); else if (c == 18) bw.put(S.clx[k], 7);
 			}
-			bw_flush(bw);
+			bw.flush();
 		}
-		bw_init(bw, S.u.outw, S.hdr_bits + S.bitoff[t] - mybits);
+		bw.init(S.u.outw, S.hdr_bits + S.bitoff[t] - mybits);
 		for (int k = 0; k < S.nsym[t]; ++k) {
 			const uint32_t s = syms[t * PNG_SUB + k];
 			if (s & 0x80000000u) {
 				int c, eb, ev;
-				len_code((int)((s >> 15) & 0x1FF), c, eb, ev); bw_put(bw, S.codes[c], S.lens[c]); bw_put(bw, (uint32_t)ev, eb);
-				dist_code((int)(s & 0x7FFF) + 1, c, eb, ev); bw_put(bw, S.codes[288 + c], S.lens[288 + c]); bw_put(bw, (uint32_t)ev, eb);
-			} else bw_put(bw, S.codes[s], S.lens[s]);
+				len_code((int)((s >> 15) & 0x1FF), c, eb, ev); bw.put(S.codes[c], S.lens[c]); bw.put((uint32_t)ev, eb);
+				dist_code((int)(s & 0x7FFF) + 1, c, eb, ev); bw.put(S.codes[288 + c], S.lens[288 + c]); bw.put((uint32_t)ev, eb);
+			} else bw.put(S.codes[s], S.lens[s]);
 		}
-		bw_flush(bw);
+		bw.flush();
 		if (t == 0) {
 			const uint32_t end = S.hdr_bits + S.bitoff[255];
-			bw_init(bw, S.u.outw, end);
-			bw_put(bw, S.codes[256], S.lens[256]);
-			bw_flush(bw);
+			bw.init(S.u.outw, end);
+			bw.put(S.codes[256], S.lens[256]);
+			bw.flush();
 			if (!last) {      // empty stored block: 3 zero bits, zeros to the byte boundary, LEN = 0, NLEN = 0xFFFF
 				const uint32_t q = (end + S.lens[256] + 3 + 7) / 8;
-				bw_init(bw, S.u.outw, 8 * (q + 2));
-				bw_put(bw, 0xFFFFu, 16);
-				bw_flush(bw);
+				bw.init(S.u.outw, 8 * (q + 2));
+				bw.put(0xFFFFu, 16);
+				bw.flush();
 			}
 		}
 		__syncthreads();
@@ -421,12 +402,7 @@ __global__ void __launch_bounds__(256) k_png_pack(const unsigned char* __restric
 	const int t = threadIdx.x, seg = blockIdx.x;
 	{ uint32_t c = (uint32_t)t; for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1; tab[t] = c; }
 	if (t == 0) { offs = 0; crc = 0; }
-	__syncthreads();
-	// exclusive scan of the chunk sizes: every workgroup sums the chunks before its own
-	unsigned long long part = 0;
-	for (int k = t; k < seg; k += 256) part += 12ull + sizes[k];
-	if (part) atomicAdd(&offs, part);
-	__syncthreads();
+	wg_slot_offset(offs, sizes, seg, 12);      // a chunk is its data and 12 bytes: length, type, CRC
 	const uint32_t size = sizes[seg];
 	unsigned char* o = out + PNG_HEAD_BYTES + offs;
 	const unsigned char* slot = slots + (long long)seg * PNG_SLOT;
@@ -513,16 +489,8 @@ int encode_device(op_ctx* ctx, CallBlocks& own, const void* src, bool is_float, 
 	{ ProfScope ps(ctx, "png pack");
 	  hipLaunchKernelGGL(k_png_pack, dim3(nseg), dim3(256), 0, st, slots, sizes, ad_a, ad_b, N, nseg, h, w, obuf, total);
 	  HIPCHK(hipGetLastError()); }
-	unsigned long long n = 0;
-	HIPCHK(hipMemcpyAsync(&n, total, sizeof(n), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	if (n < PNG_HEAD_BYTES || n > cap) OP_FAIL(OP_ERR_HIP, std::string(who) + ": the device reported an impossible file size");
-	std::unique_ptr<op_png, void (*)(op_png*)> png(new op_png, op_png_free);
-	png->bytes.resize((size_t)n);
-	{ ProfScope ps(ctx, "png D2H");
-	  HIPCHK(hipMemcpyAsync(png->bytes.data(), obuf, (size_t)n, hipMemcpyDeviceToHost, st)); }
-	HIPCHK(own.finish());
-	resolve_profile(ctx);
+	std::unique_ptr<op_png> png(new op_png);
+	if (const int r = encoded_fetch(ctx, own, obuf, total, PNG_HEAD_BYTES, cap, *png, "png D2H", who)) return r;
 	*out = png.release();
 	return OP_OK;
 }
@@ -545,22 +513,14 @@ int op_png_encode_u8(op_ctx* ctx, const unsigned char* rgb_host, int h, int w, o
 	if (!ctx || !rgb_host || !out) OP_FAIL(OP_ERR_INVALID, "op_png_encode_u8: bad argument");
 	if (h < 1 || w < 1) OP_FAIL(OP_ERR_INVALID, "op_png_encode_u8: empty image (h = 0 or w = 0): a PNG cannot hold a zero-sized image");
 	HIPCHK(hipSetDevice(ctx->device));
-	const size_t n = (size_t)h * w * 3;
 	CallBlocks own({ctx->stream});
 	unsigned char* d = nullptr;
-	HIPCHK(own.alloc(&d, n));
-	HIPCHK(hipMemcpyAsync(d, rgb_host, n, hipMemcpyHostToDevice, ctx->stream));
+	if (const int r = stage_rgb_u8(ctx, own, rgb_host, h, w, &d)) return r;
 	return encode_device(ctx, own, d, false, h, w, out, "op_png_encode_u8");
 }
 
-int64_t op_png_size(const op_png* p) { return p ? (int64_t)p->bytes.size() : 0; }
-
-int op_png_copy(op_ctx* ctx, const op_png* p, unsigned char* host) {
-	(void)ctx;
-	if (!p || !host) OP_FAIL(OP_ERR_INVALID, "op_png_copy: bad argument");
-	memcpy(host, p->bytes.data(), p->bytes.size());
-	return OP_OK;
-}
+int64_t op_png_size(const op_png* p) { return encoded_size(p); }
+int op_png_copy(op_ctx*, const op_png* p, unsigned char* host) { return encoded_copy("op_png_copy", p, host); }
 
 void op_png_free(op_png* p) { delete p; }
 

@@ -926,7 +926,7 @@ class Canvas:
         """the canvas as a PNG file (8-bit RGB, numpy_u8()'s pixels), encoded on the device (op_canvas_encode_png)"""
         h = C.c_void_p()
         check(lib().op_canvas_encode_png(self.ctx.handle, self.handle, C.byref(h)))
-        return _take_png(self.ctx, h)
+        return _take_file(self.ctx, h, "op_png")
 
     def write_png(self, path):
         data = self.png_bytes()
@@ -938,7 +938,7 @@ class Canvas:
         sampling, with restart markers), encoded on the device (op_canvas_encode_jpeg)"""
         h = C.c_void_p()
         check(lib().op_canvas_encode_jpeg(self.ctx.handle, self.handle, int(quality), _jpeg_subsampling(subsampling), C.byref(h)))
-        return _take_jpeg(self.ctx, h)
+        return _take_file(self.ctx, h, "op_jpeg")
 
     def write_jpeg(self, path, quality=90, subsampling="420"):
         data = self.jpeg_bytes(quality, subsampling)
@@ -956,23 +956,30 @@ class Canvas:
             pass
 
 
-def _take_png(ctx: Context, handle) -> bytes:
+def _take_file(ctx: Context, handle, prefix) -> bytes:
+    """the bytes of an encoded-file handle (prefix: "op_png" or "op_jpeg"), which is freed"""
+    size, copy, free = (getattr(lib(), f"{prefix}_{f}") for f in ("size", "copy", "free"))
     try:
-        out = np.empty(lib().op_png_size(handle), np.uint8)
-        check(lib().op_png_copy(ctx.handle, handle, out.ctypes.data_as(C.c_void_p)))
+        out = np.empty(size(handle), np.uint8)
+        check(copy(ctx.handle, handle, out.ctypes.data_as(C.c_void_p)))
         return out.tobytes()
     finally:
-        lib().op_png_free(handle)
+        free(handle)
+
+
+def _rgb_u8(array, who):
+    a = np.ascontiguousarray(array, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"{who}: expected (H, W, 3) bytes, got {a.shape}")
+    return a
 
 
 def encode_png_u8(ctx: Context, array) -> bytes:
     """PNG file of an (H, W, 3) uint8 array in host memory, through the device encoder (op_png_encode_u8)"""
-    a = np.ascontiguousarray(array, np.uint8)
-    if a.ndim != 3 or a.shape[2] != 3:
-        raise ValueError(f"encode_png_u8: expected (H, W, 3) bytes, got {a.shape}")
+    a = _rgb_u8(array, "encode_png_u8")
     h = C.c_void_p()
     check(lib().op_png_encode_u8(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], C.byref(h)))
-    return _take_png(ctx, h)
+    return _take_file(ctx, h, "op_png")
 
 
 JPEG_444, JPEG_420 = 0, 1      # OP_JPEG_444, OP_JPEG_420
@@ -987,24 +994,13 @@ def _jpeg_subsampling(s) -> int:
     return int(s)
 
 
-def _take_jpeg(ctx: Context, handle) -> bytes:
-    try:
-        out = np.empty(lib().op_jpeg_size(handle), np.uint8)
-        check(lib().op_jpeg_copy(ctx.handle, handle, out.ctypes.data_as(C.c_void_p)))
-        return out.tobytes()
-    finally:
-        lib().op_jpeg_free(handle)
-
-
 def encode_jpeg_u8(ctx: Context, array, quality=90, subsampling="420") -> bytes:
     """JPEG file of an (H, W, 3) uint8 array in host memory, through the device encoder (op_jpeg_encode_u8)"""
-    a = np.ascontiguousarray(array, np.uint8)
-    if a.ndim != 3 or a.shape[2] != 3:
-        raise ValueError(f"encode_jpeg_u8: expected (H, W, 3) bytes, got {a.shape}")
+    a = _rgb_u8(array, "encode_jpeg_u8")
     h = C.c_void_p()
     check(lib().op_jpeg_encode_u8(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], int(quality),
                                   _jpeg_subsampling(subsampling), C.byref(h)))
-    return _take_jpeg(ctx, h)
+    return _take_file(ctx, h, "op_jpeg")
 
 
 def blend_prepare(cfg, shapes_wh, homos, proj_method, identity_idx):

@@ -829,61 +829,58 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 template <typename Bundle>
 inline Mat32f hip_blend(const Bundle& b, bool crop = false) { return hip_blend(b, crop, std::vector<float>()); }
 
-// ---- write_rgb(fname, mat) for a .png name (lib/imgio.cc:25-41,98-113; main.cc:226-233): the file is encoded on the device
-// (op_canvas_encode_png / op_png_encode_u8) instead of by lodepng on one host thread.  Same pixels as the reference's file
-// (Color::NO -> white, v * 255 truncated), 8-bit RGB where lodepng is handed RGBA with alpha 255 and reduces it to RGB.
-inline void hip_write_png_file(const char* fname, op_png* png) {
-	std::vector<unsigned char> bytes((size_t)op_png_size(png));
-	PANO_HIP_CHECK(op_png_copy(HipContext::get(), png, bytes.data()));
-	op_png_free(png);
+// ---- write_rgb(fname, mat) (lib/imgio.cc:25-41,98-113; main.cc:30,226-233): the file is encoded on the device instead of on one
+// host thread.  What both formats share: the bytes of the handle an encoder returned go into fname and the handle is freed
+// (size / copy / release: the format's three C entries), and a host matrix is quantised as write_rgb does it (Color::NO ->
+// white, v * 255 truncated).
+template <typename File>
+inline void hip_write_encoded(const char* fname, File* file, int64_t (*size)(const File*), int (*copy)(op_ctx*, const File*, unsigned char*),
+		void (*release)(File*), const char* who) {
+	std::vector<unsigned char> bytes((size_t)size(file));
+	if (copy(HipContext::get(), file, bytes.data()) != OP_OK) hip_error_exit(who);
+	release(file);
 	FILE* f = fopen(fname, "wb");
 	if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
-		fprintf(stderr, "hip_write_png: cannot write %s\n", fname);
+		fprintf(stderr, "%s: cannot write %s\n", who, fname);
 		exit(1);
 	}
 }
+inline std::vector<unsigned char> hip_quantise_rgb(const Mat32f& mat) {
+	std::vector<unsigned char> rgb((size_t)mat.rows() * mat.cols() * 3);
+	const float* p = mat.ptr();
+	for (size_t i = 0; i < rgb.size(); ++i) rgb[i] = (unsigned char)((p[i] < 0 ? 1 : p[i]) * 255);
+	return rgb;
+}
+
+// ---- a .png name: op_canvas_encode_png / op_png_encode_u8 stand in for lodepng.  Same pixels as the reference's file, 8-bit RGB
+// where lodepng is handed RGBA with alpha 255 and reduces it to RGB.
+inline void hip_write_png_file(const char* fname, op_png* png) { hip_write_encoded(fname, png, op_png_size, op_png_copy, op_png_free, "hip_write_png"); }
 // the device canvas a blend left behind (op_blend*, op_canvas_crop): the fp32 canvas does not come back at all
 inline void hip_write_png(const char* fname, const op_canvas* canvas) {
 	op_png* png = nullptr;
 	PANO_HIP_CHECK(op_canvas_encode_png(HipContext::get(), canvas, &png));
 	hip_write_png_file(fname, png);
 }
-// write_rgb's signature: a matrix in host memory, quantised here exactly as write_png does (lib/imgio.cc:30-36)
+// write_rgb's signature: a matrix in host memory
 inline void hip_write_png(const char* fname, const Mat32f& mat) {
-	const size_t n = (size_t)mat.rows() * mat.cols() * 3;
-	std::vector<unsigned char> rgb(n);
-	const float* p = mat.ptr();
-	for (size_t i = 0; i < n; ++i) rgb[i] = (unsigned char)((p[i] < 0 ? 1 : p[i]) * 255);
+	const std::vector<unsigned char> rgb = hip_quantise_rgb(mat);
 	op_png* png = nullptr;
 	PANO_HIP_CHECK(op_png_encode_u8(HipContext::get(), rgb.data(), mat.rows(), mat.cols(), &png));
 	hip_write_png_file(fname, png);
 }
 
-// ---- write_rgb(fname, mat) for a .jpg name (lib/imgio.cc:98-113 -> CImg::save_jpeg -> libjpeg; main.cc:30,233): baseline JPEG
-// encoded on the device (op_canvas_encode_jpeg / op_jpeg_encode_u8), every byte what libjpeg writes for the same pixels,
-// quality, sampling and restart interval.  The reference's own file is quality 100 at OP_JPEG_420.
-inline void hip_write_jpeg_file(const char* fname, op_jpeg* jpg) {
-	std::vector<unsigned char> bytes((size_t)op_jpeg_size(jpg));
-	PANO_HIP_CHECK(op_jpeg_copy(HipContext::get(), jpg, bytes.data()));
-	op_jpeg_free(jpg);
-	FILE* f = fopen(fname, "wb");
-	if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
-		fprintf(stderr, "hip_write_jpeg: cannot write %s\n", fname);
-		exit(1);
-	}
-}
+// ---- a .jpg name (-> CImg::save_jpeg -> libjpeg): baseline JPEG from op_canvas_encode_jpeg / op_jpeg_encode_u8, every byte what
+// libjpeg writes for the same pixels, quality, sampling and restart interval.  The reference's own file is quality 100 at OP_JPEG_420.
+inline void hip_write_jpeg_file(const char* fname, op_jpeg* jpg) { hip_write_encoded(fname, jpg, op_jpeg_size, op_jpeg_copy, op_jpeg_free, "hip_write_jpeg"); }
 // the device canvas a blend left behind (op_blend*, op_canvas_crop)
 inline void hip_write_jpeg(const char* fname, const op_canvas* canvas, int quality = 90, int subsampling = OP_JPEG_420) {
 	op_jpeg* jpg = nullptr;
 	PANO_HIP_CHECK(op_canvas_encode_jpeg(HipContext::get(), canvas, quality, subsampling, &jpg));
 	hip_write_jpeg_file(fname, jpg);
 }
-// write_rgb's signature: a matrix in host memory, quantised here exactly as write_rgb does (lib/imgio.cc:98-113)
+// write_rgb's signature: a matrix in host memory
 inline void hip_write_jpeg(const char* fname, const Mat32f& pano, int quality = 90, int subsampling = OP_JPEG_420) {
-	const size_t n = (size_t)pano.rows() * pano.cols() * 3;
-	std::vector<unsigned char> rgb(n);
-	const float* p = pano.ptr();
-	for (size_t i = 0; i < n; ++i) rgb[i] = (unsigned char)((p[i] < 0 ? 1 : p[i]) * 255);
+	const std::vector<unsigned char> rgb = hip_quantise_rgb(pano);
 	op_jpeg* jpg = nullptr;
 	PANO_HIP_CHECK(op_jpeg_encode_u8(HipContext::get(), rgb.data(), pano.rows(), pano.cols(), quality, subsampling, &jpg));
 	hip_write_jpeg_file(fname, jpg);
