@@ -44,6 +44,10 @@ __global__ void __launch_bounds__(256) k_crop_heights(const float* __restrict__ 
 // finds them with a two-level search (own 64-chunk, chunk minima, target chunk).  The block's
 // best (area, k) keeps the reference's first-maximum rule (:222-224: strict update in k order).
 constexpr int CROP_CHUNK = 64;
+constexpr size_t CROP_LDS_MAX = 150 * 1024;         // of the 160 KiB of a CU; k_crop_lines' static arrays take 4 KiB more
+constexpr size_t crop_lds_bytes(int w) { return sizeof(int) * (size_t)(w + (w + CROP_CHUNK - 1) / CROP_CHUNK); }   // hs + cmin
+constexpr int crop_max_width() { int w = (int)(CROP_LDS_MAX / sizeof(int)); while (crop_lds_bytes(w) > CROP_LDS_MAX) --w; return w; }
+static_assert(crop_max_width() == 37809 && crop_lds_bytes(37809) == CROP_LDS_MAX, "37809 + 591 ints = 150 KiB");
 __global__ void __launch_bounds__(256) k_crop_lines(const int* __restrict__ height, int h, int w, int4* __restrict__ line_best) {
 	extern __shared__ int s_crop[];
 	int* hs = s_crop;                    // w heights of this line
@@ -182,7 +186,7 @@ int op_canvas_crop(op_ctx* ctx, const op_canvas* c, op_canvas** out, int* x0, in
 	HIPCHK(hipSetDevice(ctx->device));
 	hipStream_t st = ctx->stream;
 	const int h = c->h, w = c->w;
-	if ((size_t)(w + (w + CROP_CHUNK - 1) / CROP_CHUNK) * sizeof(int) > 150 * 1024) OP_FAIL(OP_ERR_UNSUPPORTED, "op_canvas_crop: canvas wider than 38000 px");
+	if (crop_lds_bytes(w) > CROP_LDS_MAX) OP_FAIL(OP_ERR_UNSUPPORTED, "op_canvas_crop: canvas wider than " + std::to_string(crop_max_width()) + " px");
 	CallBlocks own({ctx->stream});
 	int* d_height = nullptr; int4* d_best = nullptr; int* d_rect = nullptr;
 	HIPCHK(own.alloc(&d_height, sizeof(int) * (size_t)h * w));
@@ -193,7 +197,7 @@ int op_canvas_crop(op_ctx* ctx, const op_canvas* c, op_canvas** out, int* x0, in
 	{ ProfScope ps(ctx, "crop");
 	  hipLaunchKernelGGL(k_crop_heights, dim3((w + 255) / 256), dim3(256), 0, st, c->data, h, w, d_height);
 	  HIPCHK(hipGetLastError());
-	  const size_t lds = sizeof(int) * (size_t)(w + (w + CROP_CHUNK - 1) / CROP_CHUNK);
+	  const size_t lds = crop_lds_bytes(w);
 	  hipLaunchKernelGGL(k_crop_lines, dim3(h), dim3(256), lds, st, d_height, h, w, d_best);
 	  HIPCHK(hipGetLastError());
 	  hipLaunchKernelGGL(k_crop_pick, dim3(1), dim3(256), 0, st, d_best, h, d_rect);
