@@ -568,7 +568,47 @@ __global__ void __launch_bounds__(EXP_T) k_expand_oriented(const KeyPoint* refin
 	}
 }
 
+#ifdef OP_KP_SOLVER_PROBE
+// Test probe (tests/test_gpu_keypoint_solvers.py builds a variant of the library with this macro; the shipped build
+// does not define it): one thread takes one row-major 3 x 3 fp64 matrix through the two solvers refine_one calls and
+// writes the LU's verdict, its inverse (zeros where it refused) and the pseudo-inverse.
+__global__ void __launch_bounds__(64) k_solver_probe(const double* __restrict__ mats, int n, int* __restrict__ verdict,
+		double* __restrict__ lu_inv, double* __restrict__ pinv) {
+	const int i = blockIdx.x * 64 + threadIdx.x;
+	if (i >= n) return;
+	double m[9], inv[9], pv[9];
+	for (int k = 0; k < 9; ++k) { m[k] = mats[(long long)i * 9 + k]; inv[k] = 0.0; }
+	const bool ok = inverse3_fullpiv(m, inv);
+	pinv3_jacobi(m, pv);
+	verdict[i] = ok ? 1 : 0;
+	for (int k = 0; k < 9; ++k) { lu_inv[(long long)i * 9 + k] = inv[k]; pinv[(long long)i * 9 + k] = pv[k]; }
+}
+#endif
+
 }	// namespace
+
+#ifdef OP_KP_SOLVER_PROBE
+// host pointers in and out, on the current device's default stream; returns the hipError_t of the first failing call
+extern "C" int op_debug_kp_solver_probe(const double* mats, int n, int* verdict, double* lu_inv, double* pinv) {
+	if (!mats || !verdict || !lu_inv || !pinv || n <= 0) return (int)hipErrorInvalidValue;
+	double *d_m = nullptr, *d_lu = nullptr, *d_pv = nullptr; int* d_v = nullptr;
+	const size_t mb = sizeof(double) * 9 * (size_t)n;
+	hipError_t e = hipMalloc(&d_m, mb);
+	if (e == hipSuccess) e = hipMalloc(&d_lu, mb);
+	if (e == hipSuccess) e = hipMalloc(&d_pv, mb);
+	if (e == hipSuccess) e = hipMalloc(&d_v, sizeof(int) * (size_t)n);
+	if (e == hipSuccess) e = hipMemcpy(d_m, mats, mb, hipMemcpyHostToDevice);
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(k_solver_probe, dim3((n + 63) / 64), dim3(64), 0, 0, d_m, n, d_v, d_lu, d_pv);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpy(verdict, d_v, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(lu_inv, d_lu, mb, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(pinv, d_pv, mb, hipMemcpyDeviceToHost);
+	hipFree(d_m); hipFree(d_lu); hipFree(d_pv); hipFree(d_v);
+	return (int)e;
+}
+#endif
 
 hipError_t launch_refine(const SiftPlan& p, const int* raw, const int* raw_count, int cap, int expect,
 		KeyPoint* refined, int* refined_count, hipStream_t st) {

@@ -53,6 +53,45 @@ void orc_sift_kp(const orc_sift_run*, int which, int* ints, double* real, float*
 int orc_sift_desc_count(const orc_sift_run*);
 void orc_sift_desc(const orc_sift_run*, float* desc, double* coor);
 
+/* Branch census of one run: which branches of the keypoint chain (extrema.cc:63-168, orientation.cc:34-100,
+ * sift.cc:48-152, lib/matrix.cc:76-106) orc_sift_new took, and how often.  The counters belong to the run (the oracle
+ * is called from threads) and counting changes no result.  tests/checkers.py names them in this order. */
+enum {
+	ORC_CEN_PIVOT1 = 0,		/* 9: position row * 3 + col of the LU's first pivot */
+	ORC_CEN_PIVOT2 = 9,		/* 4: position (row - 1) * 2 + (col - 1) of its second pivot */
+	ORC_CEN_LU_RANK = 13,		/* 3: rank 0 / 1 / 2 where the LU refused the inverse */
+	ORC_CEN_PINV = 16,		/* pseudo_inverse calls */
+	ORC_CEN_ACCEPTED = 17,		/* ORC_CEN_ACCEPTED_N: offset below OFFSET_THRES after k moves (the last slot: that many or more) */
+	ORC_CEN_ACCEPTED_N = 8,
+	ORC_CEN_DEPTH_EXHAUSTED = 25,
+	ORC_CEN_SCALE_MOVES,		/* moves whose scale step is not 0 */
+	ORC_CEN_OOB_FIRST,		/* between() failed at the first iteration / after a move ... */
+	ORC_CEN_OOB_MOVED,
+	ORC_CEN_OOB_FIRST_SCALE,	/* ... and of those, the ones whose scale is out of range */
+	ORC_CEN_OOB_MOVED_SCALE,
+	ORC_CEN_OFFSET_HUGE,		/* iterations with a component of the offset above 1e9 in magnitude, or NaN */
+	ORC_CEN_CONTRAST_REJECT,
+	ORC_CEN_DET_REJECT,		/* is_edge_response: det <= 0 */
+	ORC_CEN_EDGE_REJECT,		/* is_edge_response: the ratio test */
+	ORC_CEN_ORI_BIN36,		/* samples whose bin rounded to 36 */
+	ORC_CEN_ORI_PEAK_I0,		/* peaks at histogram index 0 / 35 */
+	ORC_CEN_ORI_PEAK_I35,
+	ORC_CEN_ORI_NEWBIN_NEG,
+	ORC_CEN_ORI_PEAKS,		/* 6: keypoints with 0, 1, 2, 3, 4, >= 5 peaks */
+	ORC_CEN_ORI_MAXBIN_ZERO = ORC_CEN_ORI_PEAKS + 6,
+	ORC_CEN_DESC_HISTBIN_GE8,	/* samples with floorf(hist_bin) >= 8 */
+	ORC_CEN_DESC_CLIPPED,		/* descriptors whose window reaches over the plane's interior */
+	ORC_CEN_DESC_SUM_LE0,
+	ORC_CEN_EQUAL_CMP,		/* comparisons of the canonical sort between two keypoints equal in every key */
+	ORC_CENSUS_N
+};
+/* copies min(n, ORC_CENSUS_N) counters, returns ORC_CENSUS_N */
+int orc_sift_census(const orc_sift_run*, long* out, int n);
+/* The two 3x3 solvers of calc_kp_offset_iter on one row-major matrix: returns FullPivLU's verdict (1: invertible) with
+ * the inverse in lu_inv (zeros where it refused), and always the pseudo-inverse in pinv.  census: NULL, or ORC_CENSUS_N
+ * counters to which the LU adds its pivot positions and the rank it refused at */
+int orc_solve3(const double a[9], double lu_inv[9], double pinv[9], long* census);
+
 /* FeatureDetector::detect_feature (feature/feature.cc:20-28): descriptors + centred coords.
  * Returns K; *desc (K*128 floats) and *coor (K*2 doubles) are malloc'd, free with orc_free. */
 int orc_detect_feature(const orc_sift_cfg* cfg, const float* rgb, int h, int w,

@@ -14,6 +14,15 @@
 #define MAX_OCT 8
 #define MAX_SCALE 12
 
+/* ORC_SLIP=k compiles one deliberately wrong line into the keypoint chain (tests/test_keypoint_cases_cpu.py builds such
+ * copies to show which inputs can see the slip); the library itself is built without it.
+ * 1 inverse3_fullpiv skips the column swap when the pivot is off the diagonal, 2 a move leaves nows alone,
+ * 3 a move truncates instead of round(), 4 a keypoint without a peak emits the orientation 0,
+ * 5 identical refined keypoints are merged into one */
+#ifndef ORC_SLIP
+#define ORC_SLIP 0
+#endif
+
 typedef struct { int h, w; float* p; } plane_t;
 
 typedef struct {
@@ -36,7 +45,10 @@ struct orc_sift_run {
 	coorvec_t raw[MAX_OCT][MAX_SCALE];
 	spvec_t refined, oriented;
 	float* desc;				/* oriented.n * 128 */
+	long* census;				/* ORC_CENSUS_N branch counters of this run (oracle.h); counting only */
 };
+#define CEN(R, k) ((R)->census[k])
+static __thread long* sp_cmp_census;		/* qsort's comparator has no context argument: the sorting thread's run */
 
 void orc_sift_cfg_default(orc_sift_cfg* c) {
 	/* src/config.cfg:19-49; each literal parsed as float like ConfigParser (lib/config.cc:19-26) */
@@ -264,7 +276,8 @@ static int is_extrema(const orc_sift_run* R, int o, int s, int r, int c) {
 /* Eigen::FullPivLU<3x3> inverse as used by Matrix::inverse (lib/matrix.cc:76-87): complete
  * pivoting, rank threshold |pivot| > |maxpivot| * eps * 3, inverse = solve(I).  Restated from
  * the published algorithm (Eigen is absent; same sequence as oracle/ref_shim/Eigen/Dense). */
-static int inverse3_fullpiv(const double a[9], double inv[9]) {
+/* cen: the run's counters, or NULL */
+static int inverse3_fullpiv(const double a[9], double inv[9], long* cen) {
 	double lu[9]; memcpy(lu, a, sizeof(lu));
 	int rowt[3], colt[3], nonzero = 3; double maxpivot = 0;
 	for (int k = 0; k < 3; ++k) {
@@ -274,10 +287,17 @@ static int inverse3_fullpiv(const double a[9], double inv[9]) {
 			if (v > best) { best = v; br = i; bc = j; }
 		}
 		if (best == 0.0) { nonzero = k; for (int i = k; i < 3; ++i) rowt[i] = colt[i] = i; break; }
+		if (cen && k == 0) cen[ORC_CEN_PIVOT1 + br * 3 + bc]++;
+		if (cen && k == 1) cen[ORC_CEN_PIVOT2 + (br - 1) * 2 + (bc - 1)]++;
 		if (best > maxpivot) maxpivot = best;
 		rowt[k] = br; colt[k] = bc;
 		if (br != k) for (int j = 0; j < 3; ++j) { double t = lu[k * 3 + j]; lu[k * 3 + j] = lu[br * 3 + j]; lu[br * 3 + j] = t; }
-		if (bc != k) for (int i = 0; i < 3; ++i) { double t = lu[i * 3 + k]; lu[i * 3 + k] = lu[i * 3 + bc]; lu[i * 3 + bc] = t; }
+#if ORC_SLIP == 1
+		if (bc != k && br == bc)
+#else
+		if (bc != k)
+#endif
+			for (int i = 0; i < 3; ++i) { double t = lu[i * 3 + k]; lu[i * 3 + k] = lu[i * 3 + bc]; lu[i * 3 + bc] = t; }
 		for (int i = k + 1; i < 3; ++i) lu[i * 3 + k] /= lu[k * 3 + k];
 		for (int i = k + 1; i < 3; ++i) for (int j = k + 1; j < 3; ++j)
 			lu[i * 3 + j] -= lu[i * 3 + k] * lu[k * 3 + j];
@@ -285,7 +305,7 @@ static int inverse3_fullpiv(const double a[9], double inv[9]) {
 	double thr = fabs(maxpivot) * (DBL_EPSILON * 3);
 	int rank = 0;
 	for (int i = 0; i < nonzero; ++i) rank += (fabs(lu[i * 3 + i]) > thr);
-	if (rank != 3) return 0;
+	if (rank != 3) { if (cen) cen[ORC_CEN_LU_RANK + rank]++; return 0; }
 	for (int col = 0; col < 3; ++col) {
 		double c[3];
 		for (int i = 0; i < 3; ++i) c[i] = (i == col) ? 1.0 : 0.0;
@@ -358,7 +378,7 @@ static void kp_offset_iter(const orc_sift_run* R, int o, int x, int y, int s, do
 #undef D
 #undef DS
 	double m[9] = { dxx, dxy, dsx,  dxy, dyy, dys,  dsx, dys, dss }, inv[9];
-	if (!inverse3_fullpiv(m, inv)) pinv3_jacobi(m, inv);
+	if (!inverse3_fullpiv(m, inv, R->census)) { CEN(R, ORC_CEN_PINV)++; pinv3_jacobi(m, inv); }
 	for (int i = 0; i < 3; ++i) {		/* inv.prod(pdpx), lib/matrix.cc:40-48 */
 		double sacc = 0;
 		for (int k = 0; k < 3; ++k) sacc += inv[i * 3 + k] * delta[k];
@@ -374,20 +394,35 @@ static int calc_kp_offset(const orc_sift_run* R, sspoint_t* sp) {
 	int nowx = sp->x, nowy = sp->y, nows = sp->scale;
 	int niter = 0;
 	for (; niter < cfg->CALC_OFFSET_DEPTH; ++niter) {
-		if (!(nowx >= 1 && nowx <= w - 2) || !(nowy >= 1 && nowy <= h - 2) || !(nows >= 1 && nows <= nscale - 3))
+		if (!(nowx >= 1 && nowx <= w - 2) || !(nowy >= 1 && nowy <= h - 2) || !(nows >= 1 && nows <= nscale - 3)) {
+			int in_scale = !(nows >= 1 && nows <= nscale - 3);
+			CEN(R, niter ? ORC_CEN_OOB_MOVED : ORC_CEN_OOB_FIRST)++;
+			if (in_scale) CEN(R, niter ? ORC_CEN_OOB_MOVED_SCALE : ORC_CEN_OOB_FIRST_SCALE)++;
 			return 0;
+		}
 		kp_offset_iter(R, o, nowx, nowy, nows, offset, delta);
 		double ax = fabs(offset[0]), ay = fabs(offset[1]), az = fabs(offset[2]);
 		double mx = ay > az ? ay : az; mx = ax > mx ? ax : mx;	/* std::max(|x|, std::max(|y|,|z|)) */
+		if (!(ax <= 1e9) || !(ay <= 1e9) || !(az <= 1e9)) CEN(R, ORC_CEN_OFFSET_HUGE)++;
 		if (mx < cfg->OFFSET_THRES) break;
+		if (round(offset[2]) != 0) CEN(R, ORC_CEN_SCALE_MOVES)++;
+#if ORC_SLIP == 3
+		nowx += (int)offset[0];
+		nowy += (int)offset[1];
+		nows += (int)offset[2];
+#else
 		nowx += round(offset[0]);
 		nowy += round(offset[1]);
+#if ORC_SLIP != 2
 		nows += round(offset[2]);
+#endif
+#endif
 	}
-	if (niter == cfg->CALC_OFFSET_DEPTH) return 0;
+	if (niter == cfg->CALC_OFFSET_DEPTH) { CEN(R, ORC_CEN_DEPTH_EXHAUSTED)++; return 0; }
+	CEN(R, ORC_CEN_ACCEPTED + (niter < ORC_CEN_ACCEPTED_N ? niter : ORC_CEN_ACCEPTED_N - 1))++;
 	double dextr = offset[0] * delta[0] + offset[1] * delta[1] + offset[2] * delta[2];
 	dextr = R->dog[o][nows].p[(size_t)nowy * w + nowx] + dextr / 2;
-	if (dextr < cfg->CONTRAST_THRES) return 0;
+	if (dextr < cfg->CONTRAST_THRES) { CEN(R, ORC_CEN_CONTRAST_REJECT)++; return 0; }
 	sp->x = nowx; sp->y = nowy; sp->scale = nows;
 	sp->sf = (float)(cfg->GAUSS_SIGMA * pow(cfg->SCALE_FACTOR, ((double)nows + offset[2]) / nscale));
 	sp->rx = ((double)nowx + offset[0]) / w;
@@ -396,7 +431,7 @@ static int calc_kp_offset(const orc_sift_run* R, sspoint_t* sp) {
 }
 
 /* ---- feature/extrema.cc:152-168 is_edge_response ---- */
-static int is_edge_response(const orc_sift_cfg* cfg, int x, int y, const plane_t* img) {
+static int is_edge_response(const orc_sift_cfg* cfg, int x, int y, const plane_t* img, long* cen) {
 	int w = img->w;
 #define AT(r, c) (img->p[(size_t)(r) * w + (c)])
 	float val = AT(y, x);
@@ -405,11 +440,12 @@ static int is_edge_response(const orc_sift_cfg* cfg, int x, int y, const plane_t
 	float dxy = (AT(y + 1, x + 1) + AT(y - 1, x - 1) - AT(y + 1, x - 1) - AT(y - 1, x + 1)) / 4;
 #undef AT
 	float det = dxx * dyy - dxy * dxy;
-	if (det <= 0) return 1;
+	if (det <= 0) { cen[ORC_CEN_DET_REJECT]++; return 1; }
 	float t = dxx + dyy;
 	float tr2 = t * t;
 	float e1 = cfg->EDGE_RATIO + 1;
 	if (tr2 / det < (e1 * e1) / cfg->EDGE_RATIO) return 0;
+	cen[ORC_CEN_EDGE_REJECT]++;
 	return 1;
 }
 
@@ -428,6 +464,7 @@ static int sp_cmp(const void* a_, const void* b_) {
 	if (a->x != b->x) return a->x < b->x ? -1 : 1;
 	if (a->rx != b->rx) return a->rx < b->rx ? -1 : 1;
 	if (a->ry != b->ry) return a->ry < b->ry ? -1 : 1;
+	if (sp_cmp_census && a != b) sp_cmp_census[ORC_CEN_EQUAL_CMP]++;
 	return 0;
 }
 
@@ -453,7 +490,7 @@ static int calc_dir(const orc_sift_run* R, const sspoint_t* p, float* out /* <= 
 			if (fxx * fxx + fyy * fyy > frad * frad) continue;
 			float orient = orient_img->p[(size_t)newy * pw + newx];
 			int bin = (int)roundf(36 * halfipi * orient);
-			if (bin == 36) bin = 0;
+			if (bin == 36) { bin = 0; CEN(R, ORC_CEN_ORI_BIN36)++; }
 			float weight = expf(-(fxx * fxx + fyy * fyy) / exp_denom);
 			hist[bin] += weight * mag_img->p[(size_t)newy * pw + newx];
 		}
@@ -467,6 +504,7 @@ static int calc_dir(const orc_sift_run* R, const sspoint_t* p, float* out /* <= 
 	float maxbin = 0;
 	for (int i = 0; i < 36; ++i) if (maxbin < hist[i]) maxbin = hist[i];
 	float thres = maxbin * 0.8f;					/* ORI_HIST_PEAK_RATIO */
+	if (maxbin == 0) CEN(R, ORC_CEN_ORI_MAXBIN_ZERO)++;
 	int n = 0;
 	for (int i = 0; i < 36; ++i) {
 		float prev = hist[i == 0 ? 35 : i - 1];
@@ -474,17 +512,24 @@ static int calc_dir(const orc_sift_run* R, const sspoint_t* p, float* out /* <= 
 		float mpn = prev < next ? next : prev;		/* std::max(prev, next) */
 		if (hist[i] > thres && hist[i] > mpn) {
 			double newbin = (float)i - 0.5 + (hist[i] - prev) / (prev + next - 2 * hist[i]);
-			if (newbin < 0) newbin += 36;
-			else if (newbin >= 36) newbin -= 36;
+			if (i == 0) CEN(R, ORC_CEN_ORI_PEAK_I0)++;
+			if (i == 35) CEN(R, ORC_CEN_ORI_PEAK_I35)++;
+			if (newbin < 0) { newbin += 36; CEN(R, ORC_CEN_ORI_NEWBIN_NEG)++; }
+			else if (newbin >= 36) newbin -= 36;	/* dead: the interpolation term lies in (-1, 0), DESIGN.md */
 			out[n++] = (float)(newbin / 36 * 2 * M_PI);
 		}
 	}
+	CEN(R, ORC_CEN_ORI_PEAKS + (n < 5 ? n : 5))++;
+#if ORC_SLIP == 4
+	if (n == 0) out[n++] = 0.f;
+#endif
 	return n;
 }
 
 /* ---- feature/sift.cc:48-67 trilinear_interpolate ---- */
-static void trilinear(float xbin, float ybin, float hbin, float weight, float hist[16][8]) {
+static void trilinear(float xbin, float ybin, float hbin, float weight, float hist[16][8], long* cen) {
 	int ybinf = (int)floorf(ybin), xbinf = (int)floorf(xbin), hbinf = (int)floorf(hbin);
+	if (hbinf >= 8) cen[ORC_CEN_DESC_HISTBIN_GE8]++;
 	float ybind = ybin - ybinf, xbind = xbin - xbinf, hbind = hbin - hbinf;
 	for (int dy = 0; dy < 2; ++dy) if (ybinf + dy >= 0 && ybinf + dy <= 3) {
 		float w_y = weight * (dy ? ybind : 1 - ybind);
@@ -510,6 +555,7 @@ static void calc_descriptor(const orc_sift_run* R, const sspoint_t* p, float* ou
 	float hist[16][8];
 	memset(hist, 0, sizeof(hist));
 	float cosort = cosf(ort), sinort = sinf(ort);
+	if (p->x - radius < 1 || p->x + radius > w - 2 || p->y - radius < 1 || p->y + radius > h - 2) CEN(R, ORC_CEN_DESC_CLIPPED)++;
 	for (int xx = -radius; xx <= radius; xx++) {
 		int nowx = p->x + xx;
 		if (!(nowx >= 1 && nowx <= w - 2)) continue;
@@ -530,12 +576,13 @@ static void calc_descriptor(const orc_sift_run* R, const sspoint_t* p, float* ou
 			if (now_ort < 0) now_ort += pi2;
 			if (now_ort > pi2) now_ort -= pi2;
 			float hist_bin = now_ort * nbin_per_rad;
-			trilinear(xbin, ybin, hist_bin, weight, hist);
+			trilinear(xbin, ybin, hist_bin, weight, hist, R->census);
 		}
 	}
 	const float* hf = &hist[0][0];
 	float sum = 0;
 	for (int i = 0; i < 128; ++i) sum += hf[i];
+	if (sum <= 0) CEN(R, ORC_CEN_DESC_SUM_LE0)++;
 	for (int i = 0; i < 128; ++i) {
 		float v = hf[i] / sum;
 		out[i] = sqrtf(v) * cfg->DESC_INT_FACTOR;
@@ -545,6 +592,7 @@ static void calc_descriptor(const orc_sift_run* R, const sspoint_t* p, float* ou
 orc_sift_run* orc_sift_new(const orc_sift_cfg* cfg, const float* rgb, int h, int w) {
 	orc_sift_run* r = (orc_sift_run*)calloc(1, sizeof(orc_sift_run));
 	r->cfg = *cfg;
+	r->census = (long*)calloc(ORC_CENSUS_N, sizeof(long));
 	/* feature/feature.cc:33-35 */
 	float ratio = cfg->SIFT_WORKING_SIZE * 2.0f / (w + h);
 	int wh = (int)(h * ratio), ww = (int)(w * ratio);
@@ -577,11 +625,21 @@ orc_sift_run* orc_sift_new(const orc_sift_cfg* cfg, const float* rgb, int h, int
 				sp.x = r->raw[i][j].xy[2 * k]; sp.y = r->raw[i][j].xy[2 * k + 1];
 				sp.pyr = i; sp.scale = j;
 				if (!calc_kp_offset(r, &sp)) continue;
-				if (is_edge_response(cfg, sp.x, sp.y, &r->dog[i][sp.scale])) continue;
+				if (is_edge_response(cfg, sp.x, sp.y, &r->dog[i][sp.scale], r->census)) continue;
 				sp_push(&r->refined, &sp);
 			}
 		}
+	sp_cmp_census = r->census;
 	qsort(r->refined.v, r->refined.n, sizeof(sspoint_t), sp_cmp);
+	sp_cmp_census = NULL;
+#if ORC_SLIP == 5
+	{
+		int m = 0;
+		for (int k = 0; k < r->refined.n; ++k)
+			if (!m || sp_cmp(&r->refined.v[m - 1], &r->refined.v[k])) r->refined.v[m++] = r->refined.v[k];
+		r->refined.n = m;
+	}
+#endif
 	/* feature/orientation.cc:22-32 */
 	for (int k = 0; k < r->refined.n; ++k) {
 		float dirs[36];
@@ -606,7 +664,7 @@ void orc_sift_free(orc_sift_run* r) {
 		free(r->gauss[o][s].p); free(r->mag[o][s].p); free(r->ort[o][s].p); free(r->dog[o][s].p);
 		free(r->raw[o][s].xy);
 	}
-	free(r->refined.v); free(r->oriented.v); free(r->desc);
+	free(r->refined.v); free(r->oriented.v); free(r->desc); free(r->census);
 	free(r);
 }
 
@@ -635,6 +693,16 @@ void orc_sift_kp(const orc_sift_run* r, int which, int* ints, double* real, floa
 		real[2 * i] = v->v[i].rx; real[2 * i + 1] = v->v[i].ry;
 		fl[2 * i] = which ? v->v[i].dir : 0.f; fl[2 * i + 1] = v->v[i].sf;
 	}
+}
+int orc_sift_census(const orc_sift_run* r, long* out, int n) {
+	for (int i = 0; i < n && i < ORC_CENSUS_N; ++i) out[i] = r->census[i];
+	return ORC_CENSUS_N;
+}
+int orc_solve3(const double a[9], double lu_inv[9], double pinv[9], long* census) {
+	memset(lu_inv, 0, sizeof(double) * 9);
+	int ok = inverse3_fullpiv(a, lu_inv, census);
+	pinv3_jacobi(a, pinv);
+	return ok;
 }
 int orc_sift_desc_count(const orc_sift_run* r) { return r->oriented.n; }
 void orc_sift_desc(const orc_sift_run* r, float* desc, double* coor) {

@@ -74,6 +74,7 @@ class SiftStages:
         self.oriented = None
         self.desc = None          # (K, 128) float32
         self.coor = None          # (K, 2) float64 in [0,1)
+        self.census = None        # Oracle only: name -> count of the branches the run took (CENSUS_NAMES)
 
 
 class _StagedBase:
@@ -136,6 +137,15 @@ class _StagedBase:
         return st
 
 
+# oracle.h: ORC_CEN_*, in the enum's order (what orc_sift_census copies out)
+CENSUS_NAMES = (["pivot1_%d%d" % (r, c) for r in range(3) for c in range(3)] + ["pivot2_%d%d" % (r, c) for r in (1, 2) for c in (1, 2)] +
+                ["lu_rank_%d" % k for k in range(3)] + ["pinv_calls"] + ["accepted_%d" % k for k in range(8)] +
+                ["depth_exhausted", "scale_moves", "oob_first", "oob_moved", "oob_first_scale", "oob_moved_scale", "offset_huge",
+                 "contrast_reject", "det_reject", "edge_reject", "ori_bin36", "ori_peak_i0", "ori_peak_i35", "ori_newbin_neg"] +
+                ["ori_peaks_%s" % k for k in ("0", "1", "2", "3", "4", "5plus")] +
+                ["ori_maxbin_zero", "desc_histbin_ge8", "desc_clipped", "desc_sum_le0", "equal_cmp"])
+
+
 GAIN_NONE, GAIN_IMAGE, GAIN_BLOCK, GAIN_VIGNETTE = 0, 1, 2, 3      # oracle.h: ORC_GAIN_*
 # oracle.h: ORC_RANSAC_EXIT_*, in the enum's order (what orc_ransac_last_exit returns)
 RANSAC_EXITS = ("DEAD", "NO_HEALTHY", "FEW_INLIERS", "SINGULAR", "MATCH_RATIO_1", "POINT_RATIO_1", "MATCH_RATIO_2",
@@ -178,6 +188,8 @@ class Oracle(_StagedBase):
         lib.orc_calc_feature_batch.restype = C.c_long
         lib.orc_calc_feature_batch.argtypes = [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int]
         lib.orc_gauss_kernel.argtypes = [C.c_void_p, C.c_float, _f32p]
+        lib.orc_sift_census.argtypes = [C.c_void_p, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.c_int]
+        lib.orc_solve3.argtypes = [_f64p, _f64p, _f64p, C.c_void_p]
         for n in ("orc_expf_twin", "orc_cosf_twin", "orc_sinf_twin"):
             getattr(lib, n).restype = C.c_float; getattr(lib, n).argtypes = [C.c_float]
         lib.orc_hypotf_twin.restype = C.c_float; lib.orc_hypotf_twin.argtypes = [C.c_float, C.c_float]
@@ -305,9 +317,24 @@ class Oracle(_StagedBase):
         img = np.ascontiguousarray(img, np.float32)
         hd = self.lib.orc_sift_new(self._cp(), img.reshape(-1), img.shape[0], img.shape[1])
         try:
-            return self._collect(self.lib, hd, self.cfg, planes)
+            st = self._collect(self.lib, hd, self.cfg, planes)
+            cen = np.zeros(len(CENSUS_NAMES), np.int64)
+            assert self.lib.orc_sift_census(hd, cen, len(cen)) == len(cen)
+            st.census = dict(zip(CENSUS_NAMES, (int(v) for v in cen)))
+            return st
         finally:
             self.lib.orc_sift_free(hd)
+
+    def solve3(self, mats):
+        """the two 3x3 solvers of calc_kp_offset_iter on (n, 3, 3) float64 -> (FullPivLU's verdict (n,) int32, its inverse
+        (zeros where it refused), the pseudo-inverse, per matrix the LU's part of the census: a list of dicts)"""
+        mats = np.ascontiguousarray(mats, np.float64).reshape(-1, 9)
+        ok = np.zeros(len(mats), np.int32); lu = np.zeros((len(mats), 9)); pinv = np.zeros((len(mats), 9))
+        cen = np.zeros((len(mats), len(CENSUS_NAMES)), np.int64)
+        for i in range(len(mats)):
+            ok[i] = self.lib.orc_solve3(mats[i], lu[i], pinv[i], cen[i].ctypes.data)
+        where = [{CENSUS_NAMES[k]: 1 for k in np.flatnonzero(row)} for row in cen]
+        return ok, lu.reshape(-1, 3, 3), pinv.reshape(-1, 3, 3), where
 
     def detect_feature(self, img):
         """-> (desc (K,128) f32, coor (K,2) f64 centred image coords), canonical order."""
