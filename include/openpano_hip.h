@@ -580,6 +580,28 @@ int op_views_copy(op_ctx* ctx, const op_views* v, int i, void* host);
 int op_debug_set_jpeg_subseq_bits(op_ctx* ctx, int bits);
 int op_debug_jpeg_last_rounds(op_ctx* ctx);
 
+/* ---- EXIF ORIENTATION (additive within ABI 12) -- an opt-in beyond the reference, whose decoder (CImg -> libjpeg,
+ * lib/imgio.cc:67-90) ignores the tag: cameras store a portrait shot as a landscape frame and record the turn in EXIF tag
+ * 0x0112, so op_views_decode_jpeg yields such a view lying on its side.  DESIGN.md section 17 gives the reader's rules and
+ * the kernel.
+ * op_jpeg_exif (HOST ONLY, needs no device): orientation 1..8 (1 when absent or unreadable) and FocalLengthIn35mmFilm in mm
+ * (tag 0xA405; 0 when absent or unknown) -- the value the reference has users type into config.cfg as FOCAL_LENGTH
+ * (config.cfg:14, read by stitch/warp.cc:72).  Either pointer may be NULL.  The reader walks the segments from SOI to the first SOS, takes the first
+ * APP1 that starts with "Exif\0\0" and holds 8 more bytes, and visits IFD0 and the Exif sub-IFD (tag 0x8769) only, every
+ * offset checked against the end of that segment.  Malformed EXIF is never an error: it gives 1, 0 and OP_OK.
+ * OP_ERR_INVALID only for a NULL file, a negative size, or a file without SOI (as op_jpeg_probe).
+ * op_views_decode_jpeg_oriented: op_views_decode_jpeg with every view turned upright.  orientation == NULL: every file's own
+ * EXIF orientation.  Otherwise orientation[i] in 1..8 is used as given and 0 means "this file's EXIF"; any other value is
+ * OP_ERR_INVALID before anything is allocated.  With s the stored h x w frame (op_views_decode_jpeg's view) and o view i:
+ *   1: o[y][x] = s[y][x]            2: s[y][w-1-x]        3: s[h-1-y][w-1-x]      4: s[h-1-y][x]         (h x w)
+ *   5: o[y][x] = s[x][y]            6: s[h-1-x][y]        7: s[h-1-x][w-1-y]      8: s[x][w-1-y]         (w x h)
+ * which is what viewers do with the tag.  View i is OP_U8; op_views_image and op_views_copy report the turned shape.
+ * Everything else as op_views_decode_jpeg: all or nothing, op_last_error names the failing index, a failed call holds no
+ * device memory.  A call whose resolved orientations are all 1 runs op_views_decode_jpeg's launches and nothing else. */
+int op_jpeg_exif(const unsigned char* file, int64_t size, int* orientation, int* focal35);
+int op_views_decode_jpeg_oriented(op_ctx* ctx, const unsigned char* const* files, const int64_t* sizes, int n,
+                                  const int* orientation, op_views** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,13 +14,17 @@
 //   k_jd_dc     segmented prefix sum of the DC differences per component, reset at interval starts;
 //   k_jd_idct   dequantise + jpeg_idct_islow, a thread per block column, then per row, in LDS, to padded sample planes;
 //   k_jd_rgb    a thread per output pixel: chroma upsampling and YCbCr -> RGB, bytes written into the view.
+// op_views_decode_jpeg_oriented ends in k_jd_rgb_oriented instead when any file of the batch is to be
+// turned: the same conversion a 32 x 32 tile of the stored frame at a time, parked in LDS and written in the view's row order.
 // The symbol step, the state and the convergence rule are jpeg_dec_core.hpp's, shared with the host model and the serial
 // restatement's checks (tests/harness).  All arithmetic is integer: a view is a function of the file alone.
 #include "codec_shared.hpp"
 #include "jpeg_dec_core.hpp"
 #include "jpeg_dec_parse.hpp"
+#include "jpeg_exif.hpp"
 
 static_assert(JD_OK == OP_OK && JD_INVALID == OP_ERR_INVALID && JD_UNSUPPORTED == OP_ERR_UNSUPPORTED, "the parser returns the C-ABI's codes");
+static_assert(JX_OK == OP_OK && JX_INVALID == OP_ERR_INVALID, "the EXIF reader returns the C-ABI's codes");
 static_assert(JD_S444 == OP_JPEG_444 && JD_S420 == OP_JPEG_420 && JD_S422 == OP_JPEG_422 && JD_GREY == OP_JPEG_GREY, "the parser returns the C-ABI's samplings");
 
 namespace {
@@ -320,6 +324,65 @@ __global__ void __launch_bounds__(256) k_jd_rgb(const JdImage* __restrict__ imgs
 	o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2];
 }
 
+// ---- the last stage of op_views_decode_jpeg_oriented: k_jd_rgb's conversion, the view turned by the EXIF orientation ----
+#define JD_OT 32                     // the tile of the stored frame a workgroup of k_jd_rgb_oriented owns: JD_OT x JD_OT pixels
+#define JD_OT_PITCH (JD_OT + 1)      // dwords of a tile row in LDS: the odd pitch spreads a tile column over all 32 banks
+
+// what k_jd_rgb_oriented knows about a file beyond JdImage, which stays as the other kernels read it
+struct JdOrient { int32_t orient, oh, ow, tiles_x; };      // orient 1..8; oh x ow: the view; tiles_x: tiles across the stored frame
+
+// An orientation is three bits: the view is the stored frame mirrored in x (2, 3, 7, 8), mirrored in y (3, 4, 6, 7), then
+// transposed (5..8).  A workgroup converts its tile in source order (lanes along a stored row: coalesced reads of the sample
+// planes), parks a pixel per dword in LDS and writes the tile in the view's row order (lanes along a row of the view: every
+// row of the tile is one run of 3 * JD_OT bytes).  Both LDS passes are dword accesses of 32-lane groups: along a tile row
+// the banks are consecutive, along a tile column they step by JD_OT_PITCH = 33 = 1 (mod 32), so neither serialises.
+__global__ void __launch_bounds__(256) k_jd_rgb_oriented(const JdImage* __restrict__ imgs, const JdOrient* __restrict__ orient,
+		const unsigned char* __restrict__ planes, unsigned char* __restrict__ views, const JdStatus* __restrict__ status) {
+	__shared__ uint32_t tile[JD_OT * JD_OT_PITCH];
+	const JdImage& I = imgs[blockIdx.y];
+	const JdOrient O = orient[blockIdx.y];
+	if (status[blockIdx.y].err) return;
+	const int ty = (int)(blockIdx.x / (unsigned)O.tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)O.tiles_x);
+	const int y0 = ty * JD_OT, x0 = tx * JD_OT;
+	if (y0 >= I.h) return;                                   // uniform over the workgroup: no barrier is skipped by a part of it
+	const int r = threadIdx.x >> 5, c = threadIdx.x & 31;
+	const int cw = (I.w + I.hs - 1) / I.hs, ch = (I.h + I.vs - 1) / I.vs;
+	const int x = x0 + c;
+#pragma unroll
+	for (int k = 0; k < JD_OT; k += 8) {
+		const int y = y0 + r + k;
+		if (y >= I.h || x >= I.w) continue;
+		const int Y = planes[I.plane_off[0] + (long long)y * I.plane_w[0] + x];
+		uint32_t px;
+		if (I.ncomp == 1) px = (uint32_t)Y * 0x010101u;
+		else {
+			const int Cb = jd_chroma(planes + I.plane_off[1], I.plane_w[1], cw, ch, I.hs, I.vs, y, x);
+			const int Cr = jd_chroma(planes + I.plane_off[2], I.plane_w[2], cw, ch, I.hs, I.vs, y, x);
+			uint8_t rgb[3];
+			jd_ycc_rgb(Y, Cb, Cr, rgb);
+			px = (uint32_t)rgb[0] | (uint32_t)rgb[1] << 8 | (uint32_t)rgb[2] << 16;
+		}
+		tile[(r + k) * JD_OT_PITCH + c] = px;
+	}
+	__syncthreads();
+	const int o = O.orient - 1;
+	const bool tr = o >= 4, fx = o == 1 || o == 2 || o == 6 || o == 7, fy = o == 2 || o == 3 || o == 5 || o == 6;
+	unsigned char* out = views + I.out_off;
+#pragma unroll
+	for (int k = 0; k < JD_OT; k += 8) {
+		// (r + k, c): row and column of the tile as the view sees it; lanes run along the view's row, ascending
+		const int along = tr ? (fy ? JD_OT - 1 - c : c) : (fx ? JD_OT - 1 - c : c);
+		const int ly = tr ? along : r + k, lx = tr ? r + k : along;
+		const int sy = y0 + ly, sx = x0 + lx;
+		if (sy >= I.h || sx >= I.w) continue;
+		const int my = fy ? I.h - 1 - sy : sy, mx = fx ? I.w - 1 - sx : sx;
+		const int oy = tr ? mx : my, ox = tr ? my : mx;
+		const uint32_t px = tile[ly * JD_OT_PITCH + lx];
+		unsigned char* q = out + 3 * ((long long)oy * O.ow + ox);
+		q[0] = (unsigned char)px; q[1] = (unsigned char)(px >> 8); q[2] = (unsigned char)(px >> 16);
+	}
+}
+
 std::string err_text(uint32_t e) {
 	std::string s;
 	auto add = [&](const char* m) { if (!s.empty()) s += "; "; s += m; };
@@ -335,6 +398,130 @@ std::string err_text(uint32_t e) {
 }
 
 size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the body of op_views_decode_jpeg (oriented = false: `orientation` is not read) and of op_views_decode_jpeg_oriented; fn names the entry in messages
+int decode_views(op_ctx* ctx, const unsigned char* const* files, const int64_t* sizes, int n, bool oriented, const int* orientation,
+		const std::string& fn, op_views** out) {
+	if (!ctx || !files || !sizes || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, fn + ": bad argument");
+	*out = nullptr;
+	if (oriented && orientation)
+		for (int i = 0; i < n; ++i)
+			if (orientation[i] < 0 || orientation[i] > 8)
+				OP_FAIL(OP_ERR_INVALID, fn + ": file " + std::to_string(i) + ": orientation " + std::to_string(orientation[i]) + " is neither 0 (the file's EXIF) nor 1..8");
+	// ---- headers: every refusal happens here, before anything is allocated or launched
+	std::vector<JdImage> imgs((size_t)n);
+	std::vector<int64_t> scan_begin((size_t)n);
+	std::vector<JdOrient> orient;      // read only when some file is to be turned: otherwise the launches are op_views_decode_jpeg's
+	bool turned = false;
+	if (oriented) orient.resize((size_t)n);
+	{
+		HostScope hs(ctx, "jpegdec parse (host)");
+		for (int i = 0; i < n; ++i) {
+			if (!files[i] || sizes[i] < 0) OP_FAIL(OP_ERR_INVALID, fn + ": file " + std::to_string(i) + ": NULL data or negative size");
+			JdHeader H;
+			const int r = jd_parse(files[i], sizes[i], H);
+			if (r != JD_OK) OP_FAIL(r, fn + ": file " + std::to_string(i) + ": " + H.why);
+			jd_describe(H, imgs[i]);
+			scan_begin[i] = H.scan_begin;
+			if (oriented) {
+				int o = orientation ? orientation[i] : 0;
+				if (o == 0) { JxExif X; jx_exif(files[i], sizes[i], X); o = X.orientation; }
+				turned |= o != 1;
+				orient[i] = JdOrient{o, o >= 5 ? H.w : H.h, o >= 5 ? H.h : H.w, (H.w + JD_OT - 1) / JD_OT};
+			}
+		}
+	}
+	const uint32_t S = ctx->jpeg_subseq_bits ? (uint32_t)ctx->jpeg_subseq_bits : (uint32_t)JD_S_DEFAULT;
+	size_t in_total = 0, cmp_total = 0, iv_total = 0, sub_total = 0, coef_total = 0, plane_total = 0, out_total = 0;
+	uint32_t max_sub = 0, max_blocks = 0, max_int = 0; long long max_px = 0, max_tiles = 0;
+	for (int i = 0; i < n; ++i) {
+		JdImage& I = imgs[i];
+		I.in_off = in_total; in_total += up((size_t)I.in_len + 1, 16);
+		I.cmp_off = cmp_total; cmp_total += up((size_t)I.in_len + JD_PAD, 16);
+		I.iv_off = (uint32_t)iv_total; iv_total += (size_t)I.nint + 1;
+		I.sub_cap = (uint32_t)(((unsigned long long)I.in_len * 8 + S - 1) / S) + I.nint;
+		I.sub_off = (uint32_t)sub_total; sub_total += I.sub_cap;
+		I.coef_off = coef_total; coef_total += (size_t)I.nblocks * 64;
+		for (int c = 0; c < I.ncomp; ++c) { I.plane_off[c] = plane_total; plane_total += up((size_t)I.plane_w[c] * I.plane_h[c], 256); }
+		I.out_off = out_total; out_total += up((size_t)3 * I.h * I.w, 256);
+		max_int = std::max(max_int, I.nint); max_sub = std::max(max_sub, I.sub_cap); max_blocks = std::max(max_blocks, I.nblocks);
+		max_px = std::max(max_px, (long long)I.h * I.w);
+		max_tiles = std::max(max_tiles, (long long)((I.h + JD_OT - 1) / JD_OT) * ((I.w + JD_OT - 1) / JD_OT));
+	}
+	// k_jd_sync: about JD_WG subsequences per workgroup, never more workgroups than intervals
+	const uint32_t sync_wgs = std::max(1u, std::min(std::min(max_int, 64u), (max_sub + JD_WG - 1) / JD_WG));
+	if (iv_total >= (1ull << 31) || sub_total >= (1ull << 31)) OP_FAIL(OP_ERR_UNSUPPORTED, fn + ": the batch holds more than 2^31 restart intervals or subsequences: split it");
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	CallBlocks own({st});
+	JdImage* d_imgs = nullptr; unsigned char *d_in = nullptr, *d_cmp = nullptr, *d_planes = nullptr; char* block = nullptr;
+	uint32_t *d_iv = nullptr, *d_sf = nullptr, *d_pex = nullptr; unsigned long long *d_s0 = nullptr, *d_s1 = nullptr;
+	short* d_coef = nullptr; JdStatus* d_status = nullptr; JdOrient* d_orient = nullptr;
+	HIPCHK(own.alloc(&d_imgs, sizeof(JdImage) * (size_t)n));
+	HIPCHK(own.alloc(&d_in, in_total));
+	HIPCHK(own.alloc(&d_cmp, cmp_total));
+	HIPCHK(own.alloc(&d_iv, sizeof(uint32_t) * iv_total));
+	HIPCHK(own.alloc(&d_sf, sizeof(uint32_t) * iv_total));
+	HIPCHK(own.alloc(&d_s0, sizeof(unsigned long long) * sub_total));
+	HIPCHK(own.alloc(&d_s1, sizeof(unsigned long long) * sub_total));
+	HIPCHK(own.alloc(&d_pex, sizeof(uint32_t) * sub_total));
+	HIPCHK(own.alloc(&d_coef, sizeof(short) * coef_total));
+	HIPCHK(own.alloc(&d_planes, plane_total));
+	HIPCHK(own.alloc(&d_status, sizeof(JdStatus) * (size_t)n));
+	HIPCHK(own.alloc(&block, out_total));
+	if (turned) HIPCHK(own.alloc(&d_orient, sizeof(JdOrient) * (size_t)n));
+	{ ProfScope ps(ctx, "jpegdec H2D");
+	  HIPCHK(hipMemcpyAsync(d_imgs, imgs.data(), sizeof(JdImage) * (size_t)n, hipMemcpyHostToDevice, st));
+	  if (turned) HIPCHK(hipMemcpyAsync(d_orient, orient.data(), sizeof(JdOrient) * (size_t)n, hipMemcpyHostToDevice, st));
+	  for (int i = 0; i < n; ++i)
+		if (imgs[i].in_len) HIPCHK(hipMemcpyAsync(d_in + imgs[i].in_off, files[i] + scan_begin[i], imgs[i].in_len, hipMemcpyHostToDevice, st));
+	  HIPCHK(hipMemsetAsync(d_status, 0, sizeof(JdStatus) * (size_t)n, st));
+	  HIPCHK(hipMemsetAsync(d_coef, 0, sizeof(short) * coef_total, st)); }
+	{ ProfScope ps(ctx, "jpegdec scan");
+	  hipLaunchKernelGGL(k_jd_scan, dim3(n), dim3(JD_WG), 0, st, d_imgs, d_in, d_cmp, d_iv, d_sf, d_status, S);
+	  HIPCHK(hipGetLastError()); }
+	{ ProfScope ps(ctx, "jpegdec sync");
+	  hipLaunchKernelGGL(k_jd_sync, dim3(sync_wgs, n), dim3(JD_WG), 0, st, d_imgs, d_cmp, d_iv, d_sf, d_s0, d_s1, d_pex, d_status, S);
+	  HIPCHK(hipGetLastError()); }
+	{ ProfScope ps(ctx, "jpegdec coef");
+	  hipLaunchKernelGGL(k_jd_coef, dim3((max_sub + 255) / 256, n), dim3(256), 0, st, d_imgs, d_cmp, d_iv, d_sf, d_s0, d_pex, d_coef, d_status, S);
+	  HIPCHK(hipGetLastError()); }
+	{ ProfScope ps(ctx, "jpegdec dc");
+	  hipLaunchKernelGGL(k_jd_dc, dim3(3, n), dim3(JD_WG), 0, st, d_imgs, d_coef, d_status);
+	  HIPCHK(hipGetLastError()); }
+	{ ProfScope ps(ctx, "jpegdec idct");
+	  hipLaunchKernelGGL(k_jd_idct, dim3((max_blocks + 31) / 32, n), dim3(256), 0, st, d_imgs, d_coef, d_planes, d_status);
+	  HIPCHK(hipGetLastError()); }
+	if (!turned) {
+		ProfScope ps(ctx, "jpegdec rgb");
+		hipLaunchKernelGGL(k_jd_rgb, dim3((unsigned)((max_px + 255) / 256), n), dim3(256), 0, st, d_imgs, d_planes, (unsigned char*)block, d_status);
+		HIPCHK(hipGetLastError());
+	} else {      // the whole batch, identity included as a case
+		ProfScope ps(ctx, "jpegdec rgb oriented (k_jd_rgb_oriented)");
+		hipLaunchKernelGGL(k_jd_rgb_oriented, dim3((unsigned)max_tiles, n), dim3(256), 0, st, d_imgs, d_orient, d_planes, (unsigned char*)block, d_status);
+		HIPCHK(hipGetLastError());
+	}
+	std::vector<JdStatus> status((size_t)n);
+	HIPCHK(hipMemcpyAsync(status.data(), d_status, sizeof(JdStatus) * (size_t)n, hipMemcpyDeviceToHost, st));
+	HIPCHK(own.finish());      // the caller's files are free again
+	resolve_profile(ctx);
+	int rounds = 0;
+	for (int i = 0; i < n; ++i) {
+		if (status[i].err) OP_FAIL(OP_ERR_INVALID, fn + ": file " + std::to_string(i) + ": " + err_text(status[i].err));
+		rounds = std::max(rounds, (int)status[i].rounds);
+	}
+	ctx->jpeg_last_rounds = rounds;
+	op_views* v = new op_views;
+	v->ctx = ctx; v->block = own.release(block);
+	v->imgs.resize((size_t)n);
+	for (int i = 0; i < n; ++i) {
+		const bool swap = turned && orient[i].orient >= 5;
+		v->imgs[i] = op_image{block + imgs[i].out_off, swap ? imgs[i].w : imgs[i].h, swap ? imgs[i].h : imgs[i].w, 1, OP_U8};
+	}
+	*out = v;
+	return OP_OK;
+}
+
 
 }	// namespace
 
@@ -362,100 +549,21 @@ int op_debug_jpeg_last_rounds(op_ctx* ctx) {
 	return ctx->jpeg_last_rounds;
 }
 
-int op_views_decode_jpeg(op_ctx* ctx, const unsigned char* const* files, const int64_t* sizes, int n, op_views** out) {
-	if (!ctx || !files || !sizes || n <= 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_views_decode_jpeg: bad argument");
-	*out = nullptr;
-	// ---- headers: every refusal happens here, before anything is allocated or launched
-	std::vector<JdImage> imgs((size_t)n);
-	std::vector<int64_t> scan_begin((size_t)n);
-	{
-		HostScope hs(ctx, "jpegdec parse (host)");
-		for (int i = 0; i < n; ++i) {
-			if (!files[i] || sizes[i] < 0) OP_FAIL(OP_ERR_INVALID, "op_views_decode_jpeg: file " + std::to_string(i) + ": NULL data or negative size");
-			JdHeader H;
-			const int r = jd_parse(files[i], sizes[i], H);
-			if (r != JD_OK) OP_FAIL(r, "op_views_decode_jpeg: file " + std::to_string(i) + ": " + H.why);
-			jd_describe(H, imgs[i]);
-			scan_begin[i] = H.scan_begin;
-		}
-	}
-	const uint32_t S = ctx->jpeg_subseq_bits ? (uint32_t)ctx->jpeg_subseq_bits : (uint32_t)JD_S_DEFAULT;
-	size_t in_total = 0, cmp_total = 0, iv_total = 0, sub_total = 0, coef_total = 0, plane_total = 0, out_total = 0;
-	uint32_t max_sub = 0, max_blocks = 0, max_int = 0; long long max_px = 0;
-	for (int i = 0; i < n; ++i) {
-		JdImage& I = imgs[i];
-		I.in_off = in_total; in_total += up((size_t)I.in_len + 1, 16);
-		I.cmp_off = cmp_total; cmp_total += up((size_t)I.in_len + JD_PAD, 16);
-		I.iv_off = (uint32_t)iv_total; iv_total += (size_t)I.nint + 1;
-		I.sub_cap = (uint32_t)(((unsigned long long)I.in_len * 8 + S - 1) / S) + I.nint;
-		I.sub_off = (uint32_t)sub_total; sub_total += I.sub_cap;
-		I.coef_off = coef_total; coef_total += (size_t)I.nblocks * 64;
-		for (int c = 0; c < I.ncomp; ++c) { I.plane_off[c] = plane_total; plane_total += up((size_t)I.plane_w[c] * I.plane_h[c], 256); }
-		I.out_off = out_total; out_total += up((size_t)3 * I.h * I.w, 256);
-		max_int = std::max(max_int, I.nint); max_sub = std::max(max_sub, I.sub_cap); max_blocks = std::max(max_blocks, I.nblocks);
-		max_px = std::max(max_px, (long long)I.h * I.w);
-	}
-	// k_jd_sync: about JD_WG subsequences per workgroup, never more workgroups than intervals
-	const uint32_t sync_wgs = std::max(1u, std::min(std::min(max_int, 64u), (max_sub + JD_WG - 1) / JD_WG));
-	if (iv_total >= (1ull << 31) || sub_total >= (1ull << 31)) OP_FAIL(OP_ERR_UNSUPPORTED, "op_views_decode_jpeg: the batch holds more than 2^31 restart intervals or subsequences: split it");
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t st = ctx->stream;
-	CallBlocks own({st});
-	JdImage* d_imgs = nullptr; unsigned char *d_in = nullptr, *d_cmp = nullptr, *d_planes = nullptr; char* block = nullptr;
-	uint32_t *d_iv = nullptr, *d_sf = nullptr, *d_pex = nullptr; unsigned long long *d_s0 = nullptr, *d_s1 = nullptr;
-	short* d_coef = nullptr; JdStatus* d_status = nullptr;
-	HIPCHK(own.alloc(&d_imgs, sizeof(JdImage) * (size_t)n));
-	HIPCHK(own.alloc(&d_in, in_total));
-	HIPCHK(own.alloc(&d_cmp, cmp_total));
-	HIPCHK(own.alloc(&d_iv, sizeof(uint32_t) * iv_total));
-	HIPCHK(own.alloc(&d_sf, sizeof(uint32_t) * iv_total));
-	HIPCHK(own.alloc(&d_s0, sizeof(unsigned long long) * sub_total));
-	HIPCHK(own.alloc(&d_s1, sizeof(unsigned long long) * sub_total));
-	HIPCHK(own.alloc(&d_pex, sizeof(uint32_t) * sub_total));
-	HIPCHK(own.alloc(&d_coef, sizeof(short) * coef_total));
-	HIPCHK(own.alloc(&d_planes, plane_total));
-	HIPCHK(own.alloc(&d_status, sizeof(JdStatus) * (size_t)n));
-	HIPCHK(own.alloc(&block, out_total));
-	{ ProfScope ps(ctx, "jpegdec H2D");
-	  HIPCHK(hipMemcpyAsync(d_imgs, imgs.data(), sizeof(JdImage) * (size_t)n, hipMemcpyHostToDevice, st));
-	  for (int i = 0; i < n; ++i)
-		if (imgs[i].in_len) HIPCHK(hipMemcpyAsync(d_in + imgs[i].in_off, files[i] + scan_begin[i], imgs[i].in_len, hipMemcpyHostToDevice, st));
-	  HIPCHK(hipMemsetAsync(d_status, 0, sizeof(JdStatus) * (size_t)n, st));
-	  HIPCHK(hipMemsetAsync(d_coef, 0, sizeof(short) * coef_total, st)); }
-	{ ProfScope ps(ctx, "jpegdec scan");
-	  hipLaunchKernelGGL(k_jd_scan, dim3(n), dim3(JD_WG), 0, st, d_imgs, d_in, d_cmp, d_iv, d_sf, d_status, S);
-	  HIPCHK(hipGetLastError()); }
-	{ ProfScope ps(ctx, "jpegdec sync");
-	  hipLaunchKernelGGL(k_jd_sync, dim3(sync_wgs, n), dim3(JD_WG), 0, st, d_imgs, d_cmp, d_iv, d_sf, d_s0, d_s1, d_pex, d_status, S);
-	  HIPCHK(hipGetLastError()); }
-	{ ProfScope ps(ctx, "jpegdec coef");
-	  hipLaunchKernelGGL(k_jd_coef, dim3((max_sub + 255) / 256, n), dim3(256), 0, st, d_imgs, d_cmp, d_iv, d_sf, d_s0, d_pex, d_coef, d_status, S);
-	  HIPCHK(hipGetLastError()); }
-	{ ProfScope ps(ctx, "jpegdec dc");
-	  hipLaunchKernelGGL(k_jd_dc, dim3(3, n), dim3(JD_WG), 0, st, d_imgs, d_coef, d_status);
-	  HIPCHK(hipGetLastError()); }
-	{ ProfScope ps(ctx, "jpegdec idct");
-	  hipLaunchKernelGGL(k_jd_idct, dim3((max_blocks + 31) / 32, n), dim3(256), 0, st, d_imgs, d_coef, d_planes, d_status);
-	  HIPCHK(hipGetLastError()); }
-	{ ProfScope ps(ctx, "jpegdec rgb");
-	  hipLaunchKernelGGL(k_jd_rgb, dim3((unsigned)((max_px + 255) / 256), n), dim3(256), 0, st, d_imgs, d_planes, (unsigned char*)block, d_status);
-	  HIPCHK(hipGetLastError()); }
-	std::vector<JdStatus> status((size_t)n);
-	HIPCHK(hipMemcpyAsync(status.data(), d_status, sizeof(JdStatus) * (size_t)n, hipMemcpyDeviceToHost, st));
-	HIPCHK(own.finish());      // the caller's files are free again
-	resolve_profile(ctx);
-	int rounds = 0;
-	for (int i = 0; i < n; ++i) {
-		if (status[i].err) OP_FAIL(OP_ERR_INVALID, "op_views_decode_jpeg: file " + std::to_string(i) + ": " + err_text(status[i].err));
-		rounds = std::max(rounds, (int)status[i].rounds);
-	}
-	ctx->jpeg_last_rounds = rounds;
-	op_views* v = new op_views;
-	v->ctx = ctx; v->block = own.release(block);
-	v->imgs.resize((size_t)n);
-	for (int i = 0; i < n; ++i) v->imgs[i] = op_image{block + imgs[i].out_off, imgs[i].h, imgs[i].w, 1, OP_U8};
-	*out = v;
+int op_jpeg_exif(const unsigned char* file, int64_t size, int* orientation, int* focal35) {
+	if (!file || size < 0) OP_FAIL(OP_ERR_INVALID, "op_jpeg_exif: bad argument");
+	JxExif X;
+	if (jx_exif(file, size, X) != JX_OK) OP_FAIL(OP_ERR_INVALID, "op_jpeg_exif: no SOI: not a JPEG file");
+	if (orientation) *orientation = X.orientation;
+	if (focal35) *focal35 = X.focal35;
 	return OP_OK;
+}
+
+int op_views_decode_jpeg(op_ctx* ctx, const unsigned char* const* files, const int64_t* sizes, int n, op_views** out) {
+	return decode_views(ctx, files, sizes, n, false, nullptr, "op_views_decode_jpeg", out);
+}
+
+int op_views_decode_jpeg_oriented(op_ctx* ctx, const unsigned char* const* files, const int64_t* sizes, int n, const int* orientation, op_views** out) {
+	return decode_views(ctx, files, sizes, n, true, orientation, "op_views_decode_jpeg_oriented", out);
 }
 
 int op_views_copy(op_ctx* ctx, const op_views* v, int i, void* host) {

@@ -249,6 +249,10 @@ def lib():
         L.op_views_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.op_debug_set_jpeg_subseq_bits.argtypes = [C.c_void_p, C.c_int]
         L.op_debug_jpeg_last_rounds.argtypes = [C.c_void_p]
+    if hasattr(L, "op_views_decode_jpeg_oriented"):
+        L.op_jpeg_exif.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.op_views_decode_jpeg_oriented.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
+                                                    C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 
@@ -425,17 +429,31 @@ class Views:
         return cls(ctx, h)
 
     @classmethod
-    def decode_jpeg(cls, ctx: Context, files) -> "Views":
+    def decode_jpeg(cls, ctx: Context, files, orient=False) -> "Views":
         """files: a list of baseline JPEG files as bytes; decoded on the device into uint8 views that equal libjpeg's
         default decode byte for byte (op_views_decode_jpeg).  All or nothing: a file outside the format or a corrupt one
-        raises, naming its index."""
+        raises, naming its index.
+        orient: False: the pixels as stored.  True: every view turned upright by its file's EXIF orientation.  A sequence
+        of ints, one per file: 1..8 used as given, 0 = the file's EXIF (op_views_decode_jpeg_oriented)."""
         if not hasattr(lib(), "op_views_decode_jpeg"):
             raise OpenPanoHipError("libopenpano_hip.so was built without op_views_decode_jpeg")
         files = [bytes(f) for f in files]
         arr = (C.c_char_p * len(files))(*files)
         sizes = (C.c_int64 * len(files))(*[len(f) for f in files])
         h = C.c_void_p()
-        check(lib().op_views_decode_jpeg(ctx.handle, arr, sizes, len(files), C.byref(h)))
+        if orient is False:
+            check(lib().op_views_decode_jpeg(ctx.handle, arr, sizes, len(files), C.byref(h)))
+            return cls(ctx, h)
+        if not hasattr(lib(), "op_views_decode_jpeg_oriented"):
+            raise OpenPanoHipError("libopenpano_hip.so was built without op_views_decode_jpeg_oriented")
+        if orient is True:
+            how = None
+        else:
+            orient = [int(o) for o in orient]
+            if len(orient) != len(files):
+                raise ValueError("orient: one orientation per file")
+            how = (C.c_int * len(files))(*orient)
+        check(lib().op_views_decode_jpeg_oriented(ctx.handle, arr, sizes, len(files), how, C.byref(h)))
         return cls(ctx, h)
 
     def numpy(self, i: int) -> np.ndarray:
@@ -495,6 +513,18 @@ def jpeg_probe(data):
     h, w, s = C.c_int(), C.c_int(), C.c_int()
     check(lib().op_jpeg_probe(data, len(data), C.byref(h), C.byref(w), C.byref(s)))
     return h.value, w.value, JPEG_SAMPLING_NAMES[s.value]
+
+
+def jpeg_exif(data):
+    """(orientation, focal35) of a JPEG file's EXIF block: orientation 1..8 (1 when absent or unreadable) and
+    FocalLengthIn35mmFilm in mm (0 when absent).  Malformed EXIF is no error; only a file without SOI raises.
+    Host only: needs no device (op_jpeg_exif)."""
+    if not hasattr(lib(), "op_jpeg_exif"):
+        raise OpenPanoHipError("libopenpano_hip.so was built without op_jpeg_exif")
+    data = bytes(data)
+    o, f = C.c_int(), C.c_int()
+    check(lib().op_jpeg_exif(data, len(data), C.byref(o), C.byref(f)))
+    return o.value, f.value
 
 
 def _mk_blend_images(images):

@@ -340,7 +340,9 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 // device (op_views_decode_jpeg).  The views are bytes, every one of them libjpeg's; the caller owns the result
 // (op_views_free), or hands it to HipSIFTDetector::calc_feature(op_views*).  A file outside the format ends the program with
 // the library's message, which names its index; op_jpeg_probe tells beforehand.
-inline op_views* hip_read_jpeg_views(op_ctx* ctx, const std::vector<std::string>& paths) {
+// orient: every view turned upright by its file's EXIF orientation (op_views_decode_jpeg_oriented), which the reference's
+// decoder ignores; a view of orientation 5..8 is then w x h.
+inline op_views* hip_read_jpeg_views(op_ctx* ctx, const std::vector<std::string>& paths, bool orient = false) {
 	std::vector<std::vector<unsigned char>> data(paths.size());
 	std::vector<const unsigned char*> ptr(paths.size());
 	std::vector<int64_t> size(paths.size());
@@ -353,8 +355,21 @@ inline op_views* hip_read_jpeg_views(op_ctx* ctx, const std::vector<std::string>
 		ptr[k] = data[k].data(); size[k] = (int64_t)data[k].size();
 	}
 	op_views* v = nullptr;
-	PANO_HIP_CHECK(op_views_decode_jpeg(ctx, ptr.data(), size.data(), (int)paths.size(), &v));
+	if (orient) PANO_HIP_CHECK(op_views_decode_jpeg_oriented(ctx, ptr.data(), size.data(), (int)paths.size(), nullptr, &v));
+	else PANO_HIP_CHECK(op_views_decode_jpeg(ctx, ptr.data(), size.data(), (int)paths.size(), &v));
 	return v;
+}
+
+// The EXIF orientation (1..8; 1 when absent or unreadable) and FocalLengthIn35mmFilm (mm; 0 when absent) of a camera file
+// (op_jpeg_exif) -- the latter is what config.cfg's FOCAL_LENGTH asks the user for.  Either pointer may be NULL.  EXIF sits in
+// front of the tables, so the first megabyte of the file is all that is read.
+inline void hip_jpeg_exif(const std::string& path, int* orientation, int* focal35) {
+	FILE* f = fopen(path.c_str(), "rb");
+	if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", path.c_str()); exit(1); }      // lib/imgio.cc:68-69
+	std::vector<unsigned char> head(1 << 20);
+	head.resize(fread(head.data(), 1, head.size(), f));
+	fclose(f);
+	PANO_HIP_CHECK(op_jpeg_exif(head.data(), (int64_t)head.size(), orientation, focal35));
 }
 
 // ===================================== MATCH =====================================
@@ -1002,7 +1017,10 @@ class HipStitcher {
 		// From camera files: jpeg_paths stands in place of the Mat32f images (ImageRef(fname), stitch/imageref.hh:15-31).  Only
 		// the headers are read here (op_jpeg_probe, for the shapes); calc_feature() decodes the files on the device
 		// (hip_read_jpeg_views) and SIFT, the overlap passes and the blend read those views: build() touches no host pixel.
-		explicit HipStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u): base_seed(base_seed), jpeg_paths(paths) {
+		// apply_exif_orientation: the views are turned upright by their files' EXIF orientation, so a file of orientation
+		// 5..8 enters the job as w x h.
+		explicit HipStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u, bool apply_exif_orientation = false):
+				base_seed(base_seed), apply_exif_orientation(apply_exif_orientation), jpeg_paths(paths) {
 			if (paths.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", paths.size()); exit(1); }   // stitcherbase.hh:46-48
 			for (auto& p : paths) {
 				FILE* f = fopen(p.c_str(), "rb");
@@ -1018,6 +1036,11 @@ class HipStitcher {
 				fclose(f);
 				int h = 0, w = 0, sampling = 0;
 				if (!whole || op_jpeg_probe(head.data(), (int64_t)head.size(), &h, &w, &sampling) != OP_OK) hip_error_exit(p);
+				if (apply_exif_orientation) {
+					int o = 1;
+					if (op_jpeg_exif(head.data(), (int64_t)head.size(), &o, nullptr) != OP_OK) hip_error_exit(p);
+					if (o >= 5) std::swap(h, w);
+				}
 				imgs.emplace_back(p);
 				imgs.back()._width = w; imgs.back()._height = h;
 			}
@@ -1072,6 +1095,10 @@ class HipStitcher {
 		// resident views: calc_feature uploads the images once (bytes when they are exact k / 255, fp32 otherwise) and SIFT,
 		// the overlap passes and the blend all read that upload; off by default.  The panorama is the same bit for bit.
 		bool resident_views = false;
+		// with jpeg_paths: calc_feature() decodes every view turned upright by its file's EXIF orientation
+		// (hip_read_jpeg_views(.., true)); off by default, as the reference ignores the tag.  Set through the constructor,
+		// which takes the shapes of the views
+		bool apply_exif_orientation = false;
 		// set by the constructor that takes files: the views are decoded on the device and always resident
 		std::vector<std::string> jpeg_paths;
 
@@ -1079,7 +1106,7 @@ class HipStitcher {
 			std::vector<const Mat32f*> ptrs;
 			for (auto& r : imgs) ptrs.push_back(r.img);
 			bundle.views = nullptr;                                 // the previous upload is released by the assignment below
-			if (!jpeg_paths.empty()) feats = HipSIFTDetector().calc_feature(hip_read_jpeg_views(HipContext::get(), jpeg_paths));
+			if (!jpeg_paths.empty()) feats = HipSIFTDetector().calc_feature(hip_read_jpeg_views(HipContext::get(), jpeg_paths, apply_exif_orientation));
 			else feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
 			keypoints.resize(imgs.size());
 			for (size_t k = 0; k < imgs.size(); ++k) {

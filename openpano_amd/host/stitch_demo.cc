@@ -31,6 +31,9 @@
 // --jpeg-list PATH (anywhere; camera modes only): PATH is a text file with one baseline JPEG path per line.  The files stand in
 // place of in.bin's contents (in.bin is not opened) and are decoded on the device (HipStitcher over jpeg_paths,
 // hip_read_jpeg_views); implies --resident-views.  out.bin equals a run on an in.bin that holds the same decoded pixels.
+// --jpeg-orient (anywhere; with --jpeg-list only): every view is turned upright by its file's EXIF orientation, which the
+// reference's decoder ignores (HipStitcher::apply_exif_orientation).  out.bin equals a run on an in.bin that holds the decoded
+// pixels turned beforehand.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
@@ -175,6 +178,7 @@ int main(int argc, char** argv) {
 	const char* png_path = nullptr;
 	bool resident = false;
 	const char* jpeg_list = nullptr;
+	bool jpeg_orient = false;
 	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
@@ -182,6 +186,7 @@ int main(int argc, char** argv) {
 			else if (std::string(argv[k]) == "--vignetting") vig = true;
 			else if (std::string(argv[k]) == "--resident-views") resident = true;
 			else if (std::string(argv[k]) == "--jpeg-list" && k + 1 < argc) { jpeg_list = argv[++k]; resident = true; }
+			else if (std::string(argv[k]) == "--jpeg-orient") jpeg_orient = true;
 			else if (std::string(argv[k]) == "--png" && k + 1 < argc) png_path = argv[++k];
 			else if (std::string(argv[k]) == "--jpeg" && k + 1 < argc) g_jpeg_path = argv[++k];
 			else if (std::string(argv[k]) == "--jpeg-444") g_jpeg_444 = true;
@@ -201,7 +206,8 @@ int main(int argc, char** argv) {
 		argc = m;
 	}
 	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH [--jpeg-orient]]\n", argv[0]); return 2; }
+	if (jpeg_orient && !jpeg_list) { fprintf(stderr, "--jpeg-orient goes with --jpeg-list\n"); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	const std::string mode = argc > 4 ? argv[4] : "";
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
@@ -219,7 +225,7 @@ int main(int argc, char** argv) {
 			if (!p.empty()) paths.push_back(p);
 		}
 		fclose(fl);
-		Stitcher st(paths, base_seed);
+		Stitcher st(paths, base_seed, jpeg_orient);
 		if (mode == "camera_build") return run_build(st, argv[2], gain, gbx, gby, vig, png_path, resident);
 		return run_camera_mode(st, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
 	}
