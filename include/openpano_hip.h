@@ -528,6 +528,27 @@ int op_cyl_warp_shape(const op_config* cfg, int w, int h, double h_factor, doubl
 		int* new_w, int* new_h, double* offset);
 int op_cyl_warp(op_ctx* ctx, const op_config* cfg, const op_image* img, double h_factor, op_canvas** out);
 
+/* CYLINDER mode perspective correction (additive within ABI 12) -- replaces CylinderStitcher::perspective_correction
+ * (stitch/cylstitcher.cc:139-180), the last pixel stage of CylinderStitcher::build(): the blended canvas never leaves the device.
+ * op_canvas_upload: a device canvas from an h x w x 3 fp32 host image (a Mat32f; Color::NO = -1 allowed).  NULLs, h < 1 or
+ * w < 1 return OP_ERR_INVALID before any device work.
+ * op_perspective_homography (host only, fp64): the geometry of :140-168.  The corners (-0.5, -0.5), (-0.5, 0.5) of the bundle's
+ * first component and (0.5, -0.5), (0.5, 0.5) of its last go through to_ref_coor -- times the component's ImageRef size (the
+ * stale one after the pre-warp, not the Mat's), homo.trans, x / ref_w and y / ref_h, the flat homo2proj, times ref_w / ref_h,
+ * minus g->proj_min -- and inv is the homography that maps (0, 0), (0, canvas_h), (canvas_w, 0), (canvas_w, canvas_h) onto them
+ * in that order, h33 = 1: getPerspectiveTransform(corners, corners_std), solved by the routine RANSAC's 4-point model uses
+ * (the reference: Eigen's JacobiSVD, so its inv differs in the last digits).  corners (optional) receives the four corners as
+ * x, y pairs.  NULLs, a size below 1, three corners on one line or a non-finite entry in inv return OP_ERR_INVALID.
+ * op_canvas_perspective: the LinearBlender pass of :170-179 over the canvas itself -- one image, ROI (0, 0)-(w, h), output of
+ * the same size.  Output pixel (i, j) samples c at Homography::trans2d(j, i) (no centre offset, no z < 0 test; map_coor's
+ * bounds on the doubles), weighted as LinearBlender::run does under cfg->ORDERED_INPUT and divided as its cfg->LAZY_READ branch
+ * does: the reference's pixels, bit for bit, for the same inv.  A non-finite entry in inv returns OP_ERR_INVALID before any
+ * device work; an empty canvas gives an empty canvas. */
+int op_canvas_upload(op_ctx* ctx, const float* host_rgb, int h, int w, op_canvas** out);
+int op_perspective_homography(const op_blend_geom* g, int ref_w, int ref_h, int first_w, int first_h, const double* first_homo,
+		int last_w, int last_h, const double* last_homo, int canvas_w, int canvas_h, double* inv, double* corners);
+int op_canvas_perspective(op_ctx* ctx, const op_config* cfg, const op_canvas* c, const double* inv, op_canvas** out);
+
 /* ---- RESIDENT VIEWS -- the seam of ImageRef::load / ImageRef::img (stitch/imageref.hh:15-31): the reference loads every
  * view once and every stage reads that Mat.  An op_views holds the views of a job in library-owned device memory, each in
  * the type it arrived in (OP_F32 or OP_U8), so that SIFT, the cylinder warp, the overlap passes and every blend read ONE

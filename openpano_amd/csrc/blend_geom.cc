@@ -1,8 +1,10 @@
 // blend_geom.cc -- the O(n) geometry of the blend stage, on the host in fp64 with the host libm exactly like the reference:
 // calc_inverse_homo / update_proj_range / get_final_resolution (stitcher_image.cc:36-114), the bounds of
-// CylinderProject::project(Shape2D&) (warp.cc:46-67) and the multiband blur's taps.  Plain C++ (no HIP), built without
-// contraction; tests/harness/photometric_solve_harness.cc runs it under the sanitizers.
+// CylinderProject::project(Shape2D&) (warp.cc:46-67), the multiband blur's taps and the corners and homography of
+// CylinderStitcher::perspective_correction (cylstitcher.cc:140-168).  Plain C++ (no HIP), built without contraction;
+// tests/harness/photometric_solve_harness.cc and perspective_harness.cc run it under the sanitizers.
 #include "blend_shared.hpp"
+#include "ransac_math.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -198,6 +200,47 @@ int op_cyl_warp_shape(const op_config* cfg, int w, int h, double h_factor, doubl
 		pts[2 * k + 1] -= sy / 2;
 	}
 	*new_w = sx; *new_h = sy;
+	return OP_OK;
+}
+
+// CylinderStitcher::perspective_correction's geometry (cylstitcher.cc:140-168)
+int op_perspective_homography(const op_blend_geom* g, int ref_w, int ref_h, int first_w, int first_h, const double* first_homo,
+		int last_w, int last_h, const double* last_homo, int canvas_w, int canvas_h, double* inv, double* corners) {
+	if (!g || !first_homo || !last_homo || !inv) OP_FAIL(OP_ERR_INVALID, "op_perspective_homography: bad argument");
+	if (ref_w < 1 || ref_h < 1 || first_w < 1 || first_h < 1 || last_w < 1 || last_h < 1 || canvas_w < 1 || canvas_h < 1)
+		OP_FAIL(OP_ERR_INVALID, "op_perspective_homography: a size below 1");
+	const int refw = ref_w, refh = ref_h;
+	opransac::P2 cor[4];
+	auto to_ref_coor = [&](int k, const double* homo, int w, int h, double vx, double vy) {    // :148-156
+		vx *= w; vy *= h;
+		double hv[3], t[2];
+		htrans_host(homo, vx, vy, 1, hv);
+		hv[0] /= refw; hv[1] /= refh;
+		homo2proj_host(0, hv, t);                       // proj_method is flat by now (:25)
+		t[0] *= refw; t[1] *= refh;
+		cor[k].x = t[0] - g->proj_min[0]; cor[k].y = t[1] - g->proj_min[1];
+	};
+	to_ref_coor(0, first_homo, first_w, first_h, -0.5, -0.5);
+	to_ref_coor(1, first_homo, first_w, first_h, -0.5, 0.5);
+	to_ref_coor(2, last_homo, last_w, last_h, 0.5, -0.5);
+	to_ref_coor(3, last_homo, last_w, last_h, 0.5, 0.5);
+	if (corners) for (int k = 0; k < 4; ++k) { corners[2 * k] = cor[k].x; corners[2 * k + 1] = cor[k].y; }
+	for (int k = 0; k < 4; ++k)
+		if (!std::isfinite(cor[k].x) || !std::isfinite(cor[k].y)) OP_FAIL(OP_ERR_INVALID, "op_perspective_homography: a corner is not finite");
+	// Four points of which three lie on one line are the image of a rectangle under no homography: the 8 x 8 system is
+	// singular there, and the solver below would drop the direction and return some finite matrix.
+	for (int k = 0; k < 4; ++k) {
+		const opransac::P2 a = cor[k], b = cor[(k + 1) & 3], c = cor[(k + 2) & 3];
+		const double ux = b.x - a.x, uy = b.y - a.y, vx = c.x - a.x, vy = c.y - a.y;
+		if (std::fabs(ux * vy - uy * vx) <= 1e-12 * std::sqrt(ux * ux + uy * uy) * std::sqrt(vx * vx + vy * vy))
+			OP_FAIL(OP_ERR_INVALID, "op_perspective_homography: three corners on one line");
+	}
+	// corners_std (:164-166) and getPerspectiveTransform(corners, corners_std) (:167): from the canvas rectangle onto the corners
+	const opransac::P2 std_[4] = {{0, 0}, {0, (double)canvas_h}, {(double)canvas_w, 0}, {(double)canvas_w, (double)canvas_h}};
+	double H[9];
+	opransac::calc_transform(4, [&](int i) { return cor[i]; }, [&](int i) { return std_[i]; }, false, H);
+	for (int k = 0; k < 9; ++k) if (!std::isfinite(H[k])) OP_FAIL(OP_ERR_INVALID, "op_perspective_homography: the homography is not finite");
+	memcpy(inv, H, sizeof(H));
 	return OP_OK;
 }
 

@@ -25,6 +25,48 @@ __global__ void __launch_bounds__(256) k_cyl_project(CylParams P, const double2*
 	p[0] = c[0]; p[1] = c[1]; p[2] = c[2];
 }
 
+// ---- CylinderStitcher::perspective_correction's LinearBlender pass (cylstitcher.cc:170-179, blender.cc:24-96) over ONE image,
+// the canvas itself: thread per output pixel, 64 x 4 tiles as k_blend_linear.  The ROI is (0, 0)-(W, H) and the target has
+// that size, so both branches of run() visit every pixel.  The map is Homography::trans2d(Vec2D(j, i)) (homography.hh:53-76):
+// no centre offset and no z < 0 test (space_to_image has both); ImageToAdd::map_coor's bounds (blender.hh:39-44) are tested on
+// the doubles, BEFORE the narrowing -- -1e-50 narrows to -0.f, which in_taps would let through -- and what z == 0 makes of
+// the coordinates (NaN, +-inf) fails every comparison there or is caught by isNaN() (blender.cc:29), which looks at x.
+struct PerspMap { double inv[9]; };
+__global__ void __launch_bounds__(256) k_canvas_perspective(PerspMap M, const float* __restrict__ src, int H, int W, float* __restrict__ out,
+		int ordered_input, int lazy) {
+	const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+	const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
+	if (i >= H || j >= W) return;
+	const double* d = M.inv;
+	const double mx = (double)j, my = (double)i;
+	const double rx = d[0] * mx + d[1] * my + d[2] * 1.0;
+	const double ry = d[3] * mx + d[4] * my + d[5] * 1.0;
+	const double rz = d[6] * mx + d[7] * my + d[8] * 1.0;
+	const double denom = 1.0 / rz;
+	const double ox = rx * denom, oy = ry * denom;
+	float s0 = 0.f, s1 = 0.f, s2 = 0.f, wsum = 0.f;
+	if (!(ox < 0 || ox >= W || oy < 0 || oy >= H) && !(ox != ox)) {
+		const float r = (float)oy, c = (float)ox;
+		float col[3];
+		if (interpolate(src, H, W, r, c, col) && !(col[0] < 0)) {
+			float w = (float)(0.5 - fabs((double)(c / (float)W) - 0.5));
+			if (!ordered_input) w = (float)((double)w * (0.5 - fabs((double)(r / (float)H) - 0.5)));
+			s0 += col[0] * w; s1 += col[1] * w; s2 += col[2] * w;
+			wsum += w;
+		}
+	}
+	float* row = out + ((long long)i * W + j) * 3;
+	if (lazy) {
+		if (wsum != 0.f) { row[0] = s0 / wsum; row[1] = s1 / wsum; row[2] = s2 / wsum; }   // blender.cc:68-70
+		else { row[0] = -1.f; row[1] = -1.f; row[2] = -1.f; }
+	} else {
+		if (wsum > 0) {            // Vector::operator/(T p) = *this * (1.0 / p), lib/geometry.hh:123-124
+			const float inv = (float)(1.0 / (double)wsum);
+			row[0] = s0 * inv; row[1] = s1 * inv; row[2] = s2 * inv;
+		} else { row[0] = -1.f; row[1] = -1.f; row[2] = -1.f; }
+	}
+}
+
 // ---- crop (lib/imgproc.cc:200-235): the largest rectangle of valid pixels ----
 // Stage 1: column histograms.  height[line][k] = number of consecutive valid pixels ending at
 // (line, k); thread per column walks the lines (coalesced across k).
@@ -232,6 +274,45 @@ int op_canvas_copy_u8(op_ctx* ctx, const op_canvas* c, unsigned char* host) {
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(host, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(own.finish());
+	return OP_OK;
+}
+
+int op_canvas_upload(op_ctx* ctx, const float* host_rgb, int h, int w, op_canvas** out) {
+	if (!ctx || !host_rgb || !out || h < 1 || w < 1) OP_FAIL(OP_ERR_INVALID, "op_canvas_upload: bad argument");
+	HIPCHK(hipSetDevice(ctx->device));
+	CallBlocks own({ctx->stream});
+	float* data = nullptr;
+	const size_t bytes = sizeof(float) * 3 * (size_t)h * w;
+	if (own.alloc(&data, bytes) != hipSuccess) OP_FAIL(OP_ERR_HIP, "op_canvas_upload: allocation failed");
+	HIPCHK(hipMemcpyAsync(data, host_rgb, bytes, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(own.finish());
+	*out = new op_canvas{own.release(data), h, w, ctx->device};      // born owning its block, on the last line
+	return OP_OK;
+}
+
+int op_canvas_perspective(op_ctx* ctx, const op_config* cfg, const op_canvas* c, const double* inv, op_canvas** out) {
+	if (!ctx || !cfg || !c || !inv || !out) OP_FAIL(OP_ERR_INVALID, "op_canvas_perspective: bad argument");
+	PerspMap M;
+	for (int k = 0; k < 9; ++k) {
+		if (!std::isfinite(inv[k])) OP_FAIL(OP_ERR_INVALID, "op_canvas_perspective: inv[" + std::to_string(k) + "] is not finite");
+		M.inv[k] = inv[k];
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	const int h = c->h, w = c->w;
+	const size_t n = (size_t)h * w * 3;
+	CallBlocks own({ctx->stream});
+	float* data = nullptr;
+	if (own.alloc(&data, sizeof(float) * (n ? n : 1)) != hipSuccess) OP_FAIL(OP_ERR_HIP, "op_canvas_perspective: allocation failed");
+	if (n) {
+		ProfScope ps(ctx, "perspective");
+		hipLaunchKernelGGL(k_canvas_perspective, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, M, c->data, h, w, data,
+				cfg->ORDERED_INPUT ? 1 : 0, cfg->LAZY_READ ? 1 : 0);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(own.finish());
+	resolve_profile(ctx);
+	*out = new op_canvas{own.release(data), h, w, ctx->device};      // born owning its block, on the last line
 	return OP_OK;
 }
 

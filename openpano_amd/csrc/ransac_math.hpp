@@ -9,7 +9,13 @@
 // refit on all inliers).  The same source is compiled for host and device with
 // -ffp-contract=off, so both sides produce bit-identical homographies.
 #pragma once
+// OPR_HD: this header's own spelling of the host + device qualifiers, so that nothing it defines reaches other headers
+#if defined(__HIPCC__) || __has_include(<hip/hip_runtime.h>)
 #include <hip/hip_runtime.h>
+#define OPR_HD __host__ __device__
+#else	// plain C++ without the HIP headers on its include path (blend_geom.cc in the sanitizer programs of tests/harness)
+#define OPR_HD
+#endif
 #include <math.h>
 
 namespace opransac {
@@ -22,10 +28,10 @@ template <int NV>
 struct GivensLS {
 	double R[NV][NV];
 	double qtb[NV];
-	__host__ __device__ void reset() {
+	OPR_HD void reset() {
 		for (int i = 0; i < NV; ++i) { qtb[i] = 0; for (int j = 0; j < NV; ++j) R[i][j] = 0; }
 	}
-	__host__ __device__ void add_row(double (&a)[NV], double beta) {
+	OPR_HD void add_row(double (&a)[NV], double beta) {
 #pragma unroll
 		for (int k = 0; k < NV; ++k) {
 			const double ak = a[k];
@@ -45,7 +51,7 @@ struct GivensLS {
 			qtb[k] = t;
 		}
 	}
-	__host__ __device__ void solve(double (&x)[NV]) const {
+	OPR_HD void solve(double (&x)[NV]) const {
 		double dmax = 0;
 		for (int k = 0; k < NV; ++k) { const double d = fabs(R[k][k]); dmax = d > dmax ? d : dmax; }
 		const double tiny = dmax * 1e-13;
@@ -61,7 +67,7 @@ struct GivensLS {
 
 // scale factor sqrt(2 / mean |p|^2) of transform_estimate.cc:99-114 (no centring: :104-107)
 template <typename GetP>
-__host__ __device__ inline double norm_scale(int n, GetP getp) {
+OPR_HD inline double norm_scale(int n, GetP getp) {
 	const double sizeinv = 1.0 / n;
 	double sqrsum = 0;
 	for (int i = 0; i < n; ++i) { const P2 p = getp(i); sqrsum += (p.x * p.x + p.y * p.y) * sizeinv; }
@@ -71,7 +77,7 @@ __host__ __device__ inline double norm_scale(int n, GetP getp) {
 // calc_transform: homography (affine = false) or affine map from image-2 to image-1 points.
 // get1(i) / get2(i) return the i-th sample's point in image 1 / image 2. H is row-major 3x3.
 template <typename Get1, typename Get2>
-__host__ __device__ inline void calc_transform(int n, Get1 get1, Get2 get2, bool affine, double (&H)[9]) {
+OPR_HD inline void calc_transform(int n, Get1 get1, Get2 get2, bool affine, double (&H)[9]) {
 	const double s1 = norm_scale(n, get1), s2 = norm_scale(n, get2);
 	double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 1};
 	if (!affine) {
@@ -114,7 +120,7 @@ __host__ __device__ inline void calc_transform(int n, Get1 get1, Get2 get2, bool
 }
 
 // Homography::health (stitch/homography.hh:106-127)
-__host__ __device__ inline bool health(const double (&m)[9]) {
+OPR_HD inline bool health(const double (&m)[9]) {
 	const double HOMO_MAX_PERSPECTIVE = (double)2e-3f;
 	if (fabs(m[6]) > HOMO_MAX_PERSPECTIVE) return false;
 	if (fabs(m[7]) > HOMO_MAX_PERSPECTIVE) return false;
@@ -126,7 +132,7 @@ __host__ __device__ inline bool health(const double (&m)[9]) {
 }
 
 // one point of get_inliers (transform_estimate.cc:138-146): p2 -> image 1, squared distance to p1
-__host__ __device__ inline bool is_inlier(const double (&H)[9], P2 p1, P2 p2, double inlier_dist) {
+OPR_HD inline bool is_inlier(const double (&H)[9], P2 p1, P2 p2, double inlier_dist) {
 	const double tx = p2.x * H[0] + p2.y * H[1] + 1.0 * H[2];
 	const double ty = p2.x * H[3] + p2.y * H[4] + 1.0 * H[5];
 	const double tz = p2.x * H[6] + p2.y * H[7] + 1.0 * H[8];
@@ -138,12 +144,12 @@ __host__ __device__ inline bool is_inlier(const double (&H)[9], P2 p1, P2 p2, do
 // std::mt19937
 struct MT19937 {
 	unsigned mt[624]; int idx;
-	__host__ __device__ void seed(unsigned s) {
+	OPR_HD void seed(unsigned s) {
 		mt[0] = s;
 		for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (unsigned)i;
 		idx = 624;
 	}
-	__host__ __device__ unsigned next() {
+	OPR_HD unsigned next() {
 		if (idx >= 624) {
 			for (int i = 0; i < 624; ++i) {
 				const unsigned y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7fffffffu);

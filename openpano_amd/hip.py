@@ -237,6 +237,11 @@ def lib():
     L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
+    if hasattr(L, "op_canvas_perspective"):
+        L.op_canvas_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.op_perspective_homography.argtypes = [C.POINTER(OpBlendGeom), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.op_canvas_perspective.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     if hasattr(L, "op_views_upload"):
         L.op_views_upload.argtypes = [C.c_void_p, C.POINTER(OpImage), C.c_int, C.POINTER(C.c_void_p)]
         L.op_views_count.argtypes = [C.c_void_p]
@@ -940,6 +945,25 @@ class Canvas:
         check(lib().op_canvas_copy(self.ctx.handle, self.handle, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    @classmethod
+    def upload(cls, ctx: Context, array) -> "Canvas":
+        """a device canvas from an (H, W, 3) float32 host image, Color::NO = -1 allowed (op_canvas_upload)"""
+        a = np.ascontiguousarray(array, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"Canvas.upload: expected (H, W, 3) float32, got {a.shape}")
+        h = C.c_void_p()
+        check(lib().op_canvas_upload(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], C.byref(h)))
+        return cls(ctx, h)
+
+    def perspective(self, inv, cfg) -> "Canvas":
+        """CylinderStitcher::perspective_correction's LinearBlender pass (cylstitcher.cc:170-179) under cfg's ORDERED_INPUT and
+        LAZY_READ: pixel (i, j) of the result samples this canvas at trans2d(j, i) of ``inv`` (op_canvas_perspective)"""
+        m = np.ascontiguousarray(np.asarray(inv, np.float64).reshape(9))
+        ccfg = OpConfig.from_config(cfg)
+        h = C.c_void_p()
+        check(lib().op_canvas_perspective(self.ctx.handle, C.byref(ccfg), self.handle, m.ctypes.data_as(C.c_void_p), C.byref(h)))
+        return Canvas(self.ctx, h)
+
     def crop(self):
         """crop() of the reference (lib/imgproc.cc:200-235) -> (Canvas, (x0, y0))"""
         h = C.c_void_p(); x0, y0 = C.c_int(), C.c_int()
@@ -1245,6 +1269,25 @@ def vignette_compensate(ctx: Context, cfg, images, homos, proj_method, identity_
     call = BlendCall(ctx, cfg, images, homos, proj_method, identity_idx)
     count, moments = call.vignette_overlap_sums(stride, clip)
     return vignette_solve(len(images), count, moments, degree, sigma_n, sigma_g, sigma_v)
+
+
+def perspective_homography(proj_min, ref_wh, first_wh, first_homo, last_wh, last_homo, canvas_wh):
+    """Host geometry of ``CylinderStitcher::perspective_correction`` (cylstitcher.cc:140-168) -> (inv (3, 3), corners (4, 2)).
+    proj_min: the bundle's ``proj_range.min`` (an OpBlendGeom or an (x, y) pair); *_wh: (w, h) of the reference view, of the first
+    and the last component's ImageRef and of the canvas; *_homo: the first and the last ``component.homo``."""
+    if isinstance(proj_min, OpBlendGeom):
+        g = proj_min
+    else:
+        g = OpBlendGeom()
+        g.proj_min[0], g.proj_min[1] = float(proj_min[0]), float(proj_min[1])
+    fh = np.ascontiguousarray(np.asarray(first_homo, np.float64).reshape(9))
+    lh = np.ascontiguousarray(np.asarray(last_homo, np.float64).reshape(9))
+    inv = np.zeros(9); corners = np.zeros(8)
+    check(lib().op_perspective_homography(C.byref(g), int(ref_wh[0]), int(ref_wh[1]), int(first_wh[0]), int(first_wh[1]),
+                                          fh.ctypes.data_as(C.c_void_p), int(last_wh[0]), int(last_wh[1]), lh.ctypes.data_as(C.c_void_p),
+                                          int(canvas_wh[0]), int(canvas_wh[1]), inv.ctypes.data_as(C.c_void_p),
+                                          corners.ctypes.data_as(C.c_void_p)))
+    return inv.reshape(3, 3), corners.reshape(4, 2)
 
 
 def cyl_warp_shape(cfg, w, h, h_factor, pts=None):

@@ -1000,6 +1000,46 @@ class HipCylinderWarper {
 		const double h_factor;
 };
 
+// CylinderStitcher::perspective_correction (stitch/cylstitcher.cc:139-180) on the device: the corners of the bundle's first and
+// last component in the blended canvas (op_perspective_homography, host fp64) and the LinearBlender pass that stretches them to
+// the canvas rectangle (op_canvas_perspective) -- always the linear blender, as in the reference.  `canvas` is what the blend
+// left on the device (op_blend*); the result is a new canvas the caller owns, ready for op_canvas_crop and the encoders.
+// corners / inv (optional): the 4 x 2 corners and the 3 x 3 map, for callers that report them.  Hook 4 of INTEGRATION.md.
+template <typename Bundle>
+inline op_canvas* hip_perspective_correction(const Bundle& b, const op_canvas* canvas, double* corners = nullptr, double* inv = nullptr) {
+	op_ctx* ctx = HipContext::get();
+	const op_config cfg = hip_config_snapshot();
+	int h, w;
+	PANO_HIP_CHECK(op_canvas_dims(canvas, &h, &w));
+	op_blend_geom g;
+	memset(&g, 0, sizeof g);
+	g.proj_min[0] = b.proj_range.min.x; g.proj_min[1] = b.proj_range.min.y;
+	const auto& ref = *b.component[b.identity_idx].imgptr;
+	const auto& first = b.component.front();
+	const auto& last = b.component.back();
+	double fh[9], lh[9], m[9];
+	for (int k = 0; k < 9; ++k) { fh[k] = first.homo[k]; lh[k] = last.homo[k]; }
+	PANO_HIP_CHECK(op_perspective_homography(&g, ref.width(), ref.height(), first.imgptr->width(), first.imgptr->height(), fh,
+			last.imgptr->width(), last.imgptr->height(), lh, w, h, m, corners));
+	if (inv) memcpy(inv, m, sizeof m);
+	op_canvas* out = nullptr;
+	PANO_HIP_CHECK(op_canvas_perspective(ctx, &cfg, canvas, m, &out));
+	return out;
+}
+// perspective_correction's own signature: a matrix in host memory goes up, the corrected one comes back
+template <typename Bundle>
+inline Mat32f hip_perspective_correction(const Bundle& b, const Mat32f& img) {
+	op_ctx* ctx = HipContext::get();
+	op_canvas* cv = nullptr;
+	PANO_HIP_CHECK(op_canvas_upload(ctx, img.ptr(), img.rows(), img.cols(), &cv));
+	op_canvas* fixed = hip_perspective_correction(b, cv);
+	op_canvas_free(cv);
+	Mat32f out(img.rows(), img.cols(), 3);
+	PANO_HIP_CHECK(op_canvas_copy(ctx, fixed, out.ptr()));
+	op_canvas_free(fixed);
+	return out;
+}
+
 #ifndef OPENPANO_WITH_REFERENCE
 // ===================================== STITCHER =====================================
 // Stitcher (stitch/stitcher.hh:17-62, stitcher.cc:32-198) + StitcherBase (stitcherbase.hh:17-64),
@@ -1007,6 +1047,33 @@ class HipCylinderWarper {
 // all images, one match call and one RANSAC call for the whole pair list -- and the host stages
 // (camera estimation / bundle adjustment, pano_camera.hh) in between.  Members keep the
 // reference's names; `cameras` and `base_seed` (RANSAC seed injection) are additions.
+// ImageRef(fname) for a list of baseline JPEG files (stitch/imageref.hh:15-31): only the headers are read (op_jpeg_probe), for the
+// shapes; with apply_exif_orientation a file of orientation 5..8 enters as w x h.  Shared by the two stitchers' file constructors.
+inline void hip_jpeg_image_refs(const std::vector<std::string>& paths, bool apply_exif_orientation, std::vector<ImageRef>& imgs) {
+	for (auto& p : paths) {
+		FILE* f = fopen(p.c_str(), "rb");
+		if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", p.c_str()); exit(1); }
+		std::vector<unsigned char> head(1 << 20);      // SOF0 comes before the scan; a megabyte holds any EXIF before it
+		const size_t got = fread(head.data(), 1, head.size(), f);
+		bool whole = got < head.size();
+		if (!whole) {
+			fseek(f, 0, SEEK_END); const long all = ftell(f); fseek(f, 0, SEEK_SET);
+			head.resize((size_t)all);
+			whole = fread(head.data(), 1, head.size(), f) == head.size();
+		} else head.resize(got);
+		fclose(f);
+		int h = 0, w = 0, sampling = 0;
+		if (!whole || op_jpeg_probe(head.data(), (int64_t)head.size(), &h, &w, &sampling) != OP_OK) hip_error_exit(p);
+		if (apply_exif_orientation) {
+			int o = 1;
+			if (op_jpeg_exif(head.data(), (int64_t)head.size(), &o, nullptr) != OP_OK) hip_error_exit(p);
+			if (o >= 5) std::swap(h, w);
+		}
+		imgs.emplace_back(p);
+		imgs.back()._width = w; imgs.back()._height = h;
+	}
+}
+
 class HipStitcher {
 	public:
 		explicit HipStitcher(const std::vector<Mat32f>& mats, uint32_t base_seed = 42u): base_seed(base_seed) {
@@ -1022,28 +1089,7 @@ class HipStitcher {
 		explicit HipStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u, bool apply_exif_orientation = false):
 				base_seed(base_seed), apply_exif_orientation(apply_exif_orientation), jpeg_paths(paths) {
 			if (paths.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", paths.size()); exit(1); }   // stitcherbase.hh:46-48
-			for (auto& p : paths) {
-				FILE* f = fopen(p.c_str(), "rb");
-				if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", p.c_str()); exit(1); }
-				std::vector<unsigned char> head(1 << 20);      // SOF0 comes before the scan; a megabyte holds any EXIF before it
-				const size_t got = fread(head.data(), 1, head.size(), f);
-				bool whole = got < head.size();
-				if (!whole) {
-					fseek(f, 0, SEEK_END); const long all = ftell(f); fseek(f, 0, SEEK_SET);
-					head.resize((size_t)all);
-					whole = fread(head.data(), 1, head.size(), f) == head.size();
-				} else head.resize(got);
-				fclose(f);
-				int h = 0, w = 0, sampling = 0;
-				if (!whole || op_jpeg_probe(head.data(), (int64_t)head.size(), &h, &w, &sampling) != OP_OK) hip_error_exit(p);
-				if (apply_exif_orientation) {
-					int o = 1;
-					if (op_jpeg_exif(head.data(), (int64_t)head.size(), &o, nullptr) != OP_OK) hip_error_exit(p);
-					if (o >= 5) std::swap(h, w);
-				}
-				imgs.emplace_back(p);
-				imgs.back()._width = w; imgs.back()._height = h;
-			}
+			hip_jpeg_image_refs(paths, apply_exif_orientation, imgs);
 			for (auto& r : imgs) bundle.component.emplace_back(&r);
 		}
 		HipStitcher(const HipStitcher&) = delete;
@@ -1186,8 +1232,266 @@ class HipStitcher {
 		}
 };
 
+// ===================================== CYLINDER STITCHER =====================================
+// CylinderStitcher (stitch/cylstitcher.hh, cylstitcher.cc:20-180) + StitcherBase, standalone: the reference's mode for an ordered
+// sweep at a known focal length (config CYLINDER).  Every pixel stage runs on the device and the pixels stay there: SIFT on the
+// views, the cylinder pre-warp into device canvases (op_cyl_warp), the blend from those canvases (OP_SRC_DEVICE, h / w the
+// ImageRef's stale size and mat_h / mat_w the warp's), the perspective correction (hip_perspective_correction) and, for
+// build_canvas(true), the crop -- so that hip_write_png / hip_write_jpeg encode the result in place.  The h-factor search is the
+// reference's, float for float; its RANSAC calls are batched: one op_match_pairs for the n - 1 neighbour pairs, one
+// op_ransac_pairs per update_h_factor attempt over all right-hand pairs, one for all left-hand pairs, each over coordinates-only
+// features (the warped keypoints).  Every estimate of one build() is seeded with base_seed (the reference seeds each from
+// std::random_device).  Members keep the reference's names; `attempts`, `best_factor`, `corners`, `inv` record what a build did.
+class HipCylinderStitcher {
+	public:
+		explicit HipCylinderStitcher(const std::vector<Mat32f>& mats, uint32_t base_seed = 42u, bool resident_views = false):
+				base_seed(base_seed), resident_views(resident_views) {
+			if (mats.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", mats.size()); exit(1); }   // stitcherbase.hh:46-48
+			for (auto& m : mats) imgs.emplace_back(m);
+			for (auto& r : imgs) bundle.component.emplace_back(&r);
+		}
+		// From camera files, as HipStitcher(paths): the views are decoded on the device and are always resident
+		explicit HipCylinderStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u, bool apply_exif_orientation = false):
+				base_seed(base_seed), apply_exif_orientation(apply_exif_orientation), jpeg_paths(paths) {
+			if (paths.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", paths.size()); exit(1); }   // stitcherbase.hh:46-48
+			hip_jpeg_image_refs(paths, apply_exif_orientation, imgs);
+			for (auto& r : imgs) bundle.component.emplace_back(&r);
+		}
+		HipCylinderStitcher(const HipCylinderStitcher&) = delete;
+		HipCylinderStitcher& operator=(const HipCylinderStitcher&) = delete;
+		~HipCylinderStitcher() { free_warped(); }
+
+		// CylinderStitcher::build() (cylstitcher.cc:20-29) with the panorama left on the device; the caller owns it (op_canvas_free).
+		// crop: crop() of main.cc:226-229 on the device as well
+		op_canvas* build_canvas(bool crop = false) {
+			calc_feature();
+			bundle.identity_idx = (int)imgs.size() >> 1;
+			build_warp();
+			free_feature();
+			bundle.proj_method = ConnectedImages::flat;
+			bundle.update_proj_range();
+			op_canvas* ret = blend();
+			op_canvas* fixed = perspective_correction(ret);
+			op_canvas_free(ret);
+			if (crop) {
+				op_canvas* cc = nullptr;
+				PANO_HIP_CHECK(op_canvas_crop(HipContext::get(), fixed, &cc, nullptr, nullptr));
+				op_canvas_free(fixed);
+				fixed = cc;
+			}
+			return fixed;
+		}
+		Mat32f build() {
+			op_canvas* cv = build_canvas();
+			int h, w;
+			PANO_HIP_CHECK(op_canvas_dims(cv, &h, &w));
+			Mat32f out(h, w, 3);
+			PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), cv, out.ptr()));
+			op_canvas_free(cv);
+			return out;
+		}
+
+		std::vector<ImageRef> imgs;
+		HipFeatureSet feats;                                        // StitcherBase::feats + the resident device copy
+		std::vector<std::vector<Vec2D>> keypoints;
+		ConnectedImages bundle;
+		uint32_t base_seed;
+		// resident views (the Mat constructor): calc_feature uploads the images once and SIFT and the pre-warp read that upload;
+		// off by default.  The panorama is the same bit for bit.
+		bool resident_views = false;
+		bool apply_exif_orientation = false;
+		std::vector<std::string> jpeg_paths;
+		// what the last build did: every update_h_factor attempt, the factor the pre-warp used, the four corners and the map of
+		// the perspective correction
+		struct Attempt { float factor, slope; bool ok; };
+		std::vector<Attempt> attempts;
+		float best_factor = 1;
+		double corners[8] = {0}, inv[9] = {0};
+		// the pre-warped views, on the device (what imgs[k].img becomes in the reference, cylstitcher.cc:66-67)
+		std::vector<op_canvas*> warped;
+
+		void calc_feature() {                                       // stitcherbase.cc:9-27
+			std::vector<const Mat32f*> ptrs;
+			for (auto& r : imgs) ptrs.push_back(r.img);
+			if (!jpeg_paths.empty()) feats = HipSIFTDetector().calc_feature(hip_read_jpeg_views(HipContext::get(), jpeg_paths, apply_exif_orientation));
+			else feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
+			keypoints.resize(imgs.size());
+			for (size_t k = 0; k < imgs.size(); ++k) {
+				keypoints[k].clear();
+				for (auto& d : feats.feats[k]) keypoints[k].emplace_back(d.coor);
+			}
+		}
+		void free_feature() { feats = HipFeatureSet(); keypoints.clear(); }     // stitcherbase.cc:29-33; the views go with it
+
+		void build_warp() {                                         // cylstitcher.cc:31-87
+			op_ctx* ctx = HipContext::get();
+			const op_config cfg = hip_config_snapshot();
+			const int n = (int)imgs.size(), mid = bundle.identity_idx;
+			for (int i = 0; i < n; ++i) bundle.component[i].homo = Homography::I();
+			attempts.clear();
+
+			// matches[k]: k, k + 1 (:41-42), once; the right-hand lists as they are and the left-hand ones reversed (:73) become
+			// the two handles the RANSAC calls read
+			std::vector<int> pr;
+			for (int k = 0; k + 1 < n; ++k) { pr.push_back(k); pr.push_back(k + 1); }
+			op_matches* all = nullptr;
+			PANO_HIP_CHECK(op_match_pairs(ctx, &cfg, feats.handle, pr.data(), n - 1, &all));
+			std::vector<int64_t> off((size_t)n);
+			std::vector<int> idx((size_t)op_matches_total(all) * 2 + 2);
+			PANO_HIP_CHECK(op_matches_copy_all(all, idx.data(), off.data()));
+			op_matches_free(all);
+			for (int k = 0; k < mid; ++k) for (int64_t q = off[k]; q < off[k + 1]; ++q) std::swap(idx[2 * q], idx[2 * q + 1]);
+			std::vector<const int*> lists; std::vector<int> counts;
+			for (int k = 0; k + 1 < n; ++k) { lists.push_back(idx.data() + 2 * off[k]); counts.push_back((int)(off[k + 1] - off[k])); }
+			right_matches = left_matches = nullptr;
+			if (n - 1 - mid > 0) PANO_HIP_CHECK(op_matches_from_host(lists.data() + mid, counts.data() + mid, n - 1 - mid, &right_matches));
+			if (mid > 0) PANO_HIP_CHECK(op_matches_from_host(lists.data(), counts.data(), mid, &left_matches));
+
+			std::vector<Homography> bestmat;
+			float minslope = std::numeric_limits<float>::max();
+			float bestfactor = 1;
+			if (n - mid > 1) {
+				float newfactor = 1;
+				float slope = update_h_factor(newfactor, minslope, bestfactor, bestmat);
+				if (bestmat.empty()) { fprintf(stderr, "error: Failed to find hfactor\n"); exit(1); }
+				float centerx1 = 0, centerx2 = bestmat[0].trans2d(Vec2D(0, 0)).x;
+				float order = (centerx2 > centerx1 ? 1 : -1);
+				for (int k = 0; k < 3; ++k) {
+					if (fabs(slope) < config::SLOPE_PLAIN) break;
+					newfactor += (slope < 0 ? order : -order) / (5 * pow(2, k));
+					slope = update_h_factor(newfactor, minslope, bestfactor, bestmat);
+				}
+			}
+			fprintf(stderr, "Best hfactor: %lf\n", bestfactor);
+			best_factor = bestfactor;
+			HipCylinderWarper warper(bestfactor);
+			// :65-67: the pixels into device canvases, the keypoints in place; the ImageRef sizes stay what load() left
+			free_warped();
+			warped.assign((size_t)n, nullptr);
+			for (int k = 0; k < n; ++k) {
+				op_image im{imgs[k].img ? imgs[k].img->ptr() : nullptr, imgs[k].height(), imgs[k].width(), 0, OP_F32};
+				if (feats.views) PANO_HIP_CHECK(op_views_image(feats.views, k, &im));
+				PANO_HIP_CHECK(op_cyl_warp(ctx, &cfg, &im, (double)bestfactor, &warped[k]));
+				Shape2D shape = imgs[k].shape();
+				warper.warp(shape, keypoints[k]);
+			}
+
+			// accumulate
+			for (int k = mid + 1; k < n; ++k) bundle.component[k].homo = bestmat[k - mid - 1];
+			if (mid > 0) {      // :72-83, one call: pair (i + 1, i) with the reversed list, the ImageRefs' stale shapes
+				std::vector<int> pairs, shapes;                     // over views 0 .. mid, the only ones these pairs read
+				for (int i = 0; i < mid; ++i) { pairs.push_back(i + 1); pairs.push_back(i); }
+				for (int i = 0; i <= mid; ++i) { shapes.push_back(imgs[i].width()); shapes.push_back(imgs[i].height()); }
+				std::vector<Homography> homo;
+				const int failed = estimate(left_matches, keypoints.data(), mid + 1, pairs, shapes, homo);
+				// Can match before, but not here. This would be a bug.
+				if (failed >= 0) { fprintf(stderr, "error: Failed to match between image %d and %d.\n", failed, failed + 1); exit(1); }
+				for (int i = 0; i < mid; ++i) bundle.component[i].homo = homo[i];
+			}
+			for (int i = mid - 2; i >= 0; --i) bundle.component[i].homo = bundle.component[i + 1].homo * bundle.component[i].homo;
+			bundle.calc_inverse_homo();
+			op_matches_free(right_matches); op_matches_free(left_matches);
+			right_matches = left_matches = nullptr;
+		}
+
+		// cylstitcher.cc:89-137
+		float update_h_factor(float nowfactor, float& minslope, float& bestfactor, std::vector<Homography>& mat) {
+			const int n = (int)imgs.size(), mid = bundle.identity_idx;
+			const int start = mid, end = n, len = end - start;
+			std::vector<int> shapes;                                // nowimgs[k].shape() after the warp
+			std::vector<std::vector<Vec2D>> nowkpts(keypoints.begin() + start, keypoints.begin() + end);
+			HipCylinderWarper warper(nowfactor);
+			for (int k = 0; k < len; ++k) {
+				Shape2D s = imgs[start + k].shape();
+				warper.warp(s, nowkpts[k]);
+				shapes.push_back(s.w); shapes.push_back(s.h);
+			}
+			std::vector<int> pairs;                                 // in nowimgs' numbering: only views start .. n - 1 go up
+			for (int k = 1; k < len; ++k) { pairs.push_back(k - 1); pairs.push_back(k); }
+			std::vector<Homography> nowmat;                         // size = len - 1
+			const bool failed = estimate(right_matches, nowkpts.data(), len, pairs, shapes, nowmat) >= 0;
+			if (failed) { attempts.push_back(Attempt{nowfactor, 0.f, false}); return 0; }
+			for (int k = 1; k < len - 1; ++k) nowmat[k] = nowmat[k - 1] * nowmat[k];    // transform to nowimgs[0] == imgs[mid]
+			// check the slope of the result image
+			const Vec2D center2 = nowmat.back().trans2d(Vec2D(0, 0));
+			const float slope = center2.y / center2.x;
+			fprintf(stderr, "slope: %lf\n", slope);
+			attempts.push_back(Attempt{nowfactor, slope, true});
+			const float aslope = fabs(slope);
+			if (aslope < minslope) {                                // update_min(minslope, fabs(slope))
+				minslope = aslope;
+				bestfactor = nowfactor;
+				mat = std::move(nowmat);
+			}
+			return slope;
+		}
+
+		// bundle.blend() (stitcher_image.cc:116-155) from the pre-warped canvases, flat projection; honours config::MULTIBAND
+		op_canvas* blend() {
+			op_ctx* ctx = HipContext::get();
+			const op_config cfg = hip_config_snapshot();
+			const int n = (int)imgs.size();
+			const Vec2D res = bundle.get_final_resolution();
+			op_blend_geom g;
+			g.proj_method = (int)bundle.proj_method;
+			g.proj_min[0] = bundle.proj_range.min.x; g.proj_min[1] = bundle.proj_range.min.y;
+			g.proj_max[0] = bundle.proj_range.max.x; g.proj_max[1] = bundle.proj_range.max.y;
+			g.resolution[0] = res.x; g.resolution[1] = res.y;
+			std::vector<op_blend_image> ims((size_t)n);
+			for (int i = 0; i < n; ++i) {
+				auto& c = bundle.component[i];
+				ims[i].data = op_canvas_device(warped[i]); ims[i].on_device = OP_SRC_DEVICE;
+				ims[i].h = c.imgptr->height(); ims[i].w = c.imgptr->width();
+				PANO_HIP_CHECK(op_canvas_dims(warped[i], &ims[i].mat_h, &ims[i].mat_w));
+				for (int k = 0; k < 9; ++k) ims[i].homo_inv[k] = c.homo_inv[k];
+				ims[i].range[0] = c.range.min.x; ims[i].range[1] = c.range.min.y; ims[i].range[2] = c.range.max.x; ims[i].range[3] = c.range.max.y;
+			}
+			op_canvas* cv = nullptr;
+			PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
+			return cv;
+		}
+
+		// cylstitcher.cc:139-180; records corners and inv
+		op_canvas* perspective_correction(const op_canvas* img) { return hip_perspective_correction(bundle, img, corners, inv); }
+
+	private:
+		op_matches *right_matches = nullptr, *left_matches = nullptr;   // alive inside build_warp only
+		void free_warped() { for (op_canvas* c : warped) op_canvas_free(c); warped.clear(); }
+		// One op_ransac_pairs over coordinates-only features (INTEGRATION hook 3) of the n views the pairs read: kpts and (w, h)
+		// per view, the pair list that goes with `m`, all three in the numbering of those n views.  homo[p] = the estimate of
+		// pair p; returns the second view of the first pair that failed, -1 when none did
+		int estimate(const op_matches* m, const std::vector<Vec2D>* kpts, int n, const std::vector<int>& pairs, const std::vector<int>& shapes,
+				std::vector<Homography>& homo) {
+			op_ctx* ctx = HipContext::get();
+			const op_config cfg = hip_config_snapshot();
+			const int np = (int)pairs.size() / 2;
+			std::vector<std::vector<double>> flat((size_t)n);
+			std::vector<const double*> cp((size_t)n); std::vector<int> counts((size_t)n);
+			for (int k = 0; k < n; ++k) {
+				counts[k] = (int)kpts[k].size();
+				flat[k].resize((size_t)counts[k] * 2 + 2);
+				for (int i = 0; i < counts[k]; ++i) { flat[k][2 * i] = kpts[k][i].x; flat[k][2 * i + 1] = kpts[k][i].y; }
+				cp[k] = flat[k].data();
+			}
+			op_features* f = nullptr;
+			PANO_HIP_CHECK(op_features_from_host(ctx, nullptr, cp.data(), counts.data(), n, &f));
+			const std::vector<uint32_t> seeds((size_t)np, base_seed);
+			op_ransac_result* r = nullptr;
+			PANO_HIP_CHECK(op_ransac_pairs(ctx, &cfg, f, m, pairs.data(), np, shapes.data(), seeds.data(), 0, &r));
+			homo.assign((size_t)np, Homography::I());
+			int failed = -1;
+			for (int p = 0; p < np; ++p) {
+				if (!op_ransac_ok(r, p)) { if (failed < 0) failed = pairs[2 * p + 1]; continue; }
+				PANO_HIP_CHECK(op_ransac_homo(r, p, homo[p].data));
+			}
+			op_ransac_free(r); op_features_free(f);
+			return failed;
+		}
+};
+
 // standalone builds read like the reference
 using Stitcher = HipStitcher;
+using CylinderStitcher = HipCylinderStitcher;
 using SIFTDetector = HipSIFTDetector;
 using PairWiseMatcher = HipPairWiseMatcher;
 using TransformEstimation = HipTransformEstimation;

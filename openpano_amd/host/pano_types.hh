@@ -46,6 +46,7 @@ inline float INLIER_IN_MATCH_RATIO = 0.1f, INLIER_IN_POINTS_RATIO = 0.04f;
 inline int MULTIBAND = 0;
 inline int MULTIPASS_BA = 1;
 inline float LM_LAMBDA = 5.f;
+inline float SLOPE_PLAIN = 8e-3f;
 }	// namespace config
 
 template <typename T>

@@ -4,7 +4,7 @@
 //   replaced here by chaining the pairwise homographies to the middle image] -> blend,
 // written with the reference's class and method names.
 //
-//   stitch_demo <in.bin> <out.bin> [base_seed] [camera|camera_ordered]
+//   stitch_demo <in.bin> <out.bin> [base_seed] [camera|camera_ordered|camera_build|cylinder|cylinder_build]
 // ("camera_ordered": ORDERED_INPUT 1 as in BASELINE configs 2-3 -- only (i, i+1 mod n) are matched,
 // Stitcher::linear_pairwise_match, stitcher.cc:115-136; head and tail need not connect.)
 // With "camera" the program runs the ESTIMATE_CAMERA branch of Stitcher::build() instead (BASELINE
@@ -13,6 +13,19 @@
 // ppy, R) in place of the chain homographies, before the canvas.
 // "camera_build": the same branch through HipStitcher::build() itself (Stitcher st(mats); st.build()); out.bin then
 // holds only int32 H, W ; H*W*3 f32 [; n*3 f32 gains under --gain-compensation, n*B*3 under --gain-blocks].
+// "cylinder": CylinderStitcher::build() (stitch/cylstitcher.cc:20-29; CYLINDER 1, ESTIMATE_CAMERA 0, TRANS 0, ORDERED_INPUT 1,
+// LAZY_READ 0) stage by stage through HipCylinderStitcher, from in.bin or --jpeg-list [--jpeg-orient]; accepts --resident-views,
+// --png, --jpeg.. and --crop, and encodes the files from the device canvas.  out.bin then holds
+//          int32 n ; per view int32 K ; K*2 f64 keypoints as detected
+//          int32 number of update_h_factor attempts ; per attempt f32 factor, f32 slope, int32 ok ; f32 best factor
+//          n*9 f64 component.homo ; int32 H, W ; H*W*3 f32 (the blend, before the correction)
+//          8 f64 corners ; 9 f64 inv ; int32 H, W ; H*W*3 f32 (the panorama)
+// "cylinder_build": the same through HipCylinderStitcher::build() itself, then hip_perspective_correction(bundle, Mat32f) on the
+// blend of that build, then build_canvas(crop) on the same object, from which the files are encoded; out.bin then holds three
+// times int32 H, W ; H*W*3 f32: the first two the panorama, the third the panorama cropped under --crop.  --profile (this mode
+// only) prints the context's stage times and the wall time of that build_canvas() call to stderr.
+// --crop (anywhere; cylinder modes only): the files of --png / --jpeg hold the panorama cropped to its largest valid rectangle
+// (crop(), lib/imgproc.cc:200-235, on the device); out.bin is the same with and without it.
 // --gain-compensation (anywhere on the line): exposure compensation before the blend (HipStitcher::gain_compensation,
 // hip_gain_compensate: an extension beyond the reference); out.bin then ends with n*3 f32 gains after the canvas.
 // --gain-blocks BXxBY (anywhere; implies --gain-compensation): block gain compensation on a BX x BY grid per image
@@ -39,6 +52,7 @@
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
 //          int32 H, W ; H*W*3 f32 (flat-projection linear blend of the chain that connected; H=W=0 if none)
 // tests/test_gpu_host_cpp.py runs it on the GPU box and checks every section against the oracle.
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -171,6 +185,108 @@ static int run_build(Stitcher& st, const char* out_path, bool gain, int gbx, int
 	return 0;
 }
 
+// CylinderStitcher::build() (stitch/cylstitcher.cc:20-29), stage by stage so that every intermediate can be written out
+static void put_canvas(FILE* fo, const op_canvas* cv) {
+	int h, w;
+	PANO_HIP_CHECK(op_canvas_dims(cv, &h, &w));
+	std::vector<float> px((size_t)h * w * 3);
+	if (!px.empty()) PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), cv, px.data()));
+	put1<int32_t>(fo, h); put1<int32_t>(fo, w);
+	put(fo, px.data(), px.size());
+}
+static int run_cylinder_mode(CylinderStitcher& st, const char* out_path, const char* png_path, bool resident, bool crop) {
+	st.resident_views = resident;
+	FILE* fo = fopen(out_path, "wb");
+	if (!fo) { perror(out_path); return 2; }
+	const int n = (int)st.imgs.size();
+	st.calc_feature();
+	put1<int32_t>(fo, n);
+	for (int k = 0; k < n; ++k) {
+		put1<int32_t>(fo, (int32_t)st.keypoints[k].size());
+		for (auto& p : st.keypoints[k]) { double c[2] = {p.x, p.y}; put(fo, c, 2); }
+		fprintf(stderr, "Image %d has %zu features\n", k, st.keypoints[k].size());
+	}
+	st.bundle.identity_idx = n >> 1;
+	st.build_warp();
+	st.free_feature();
+	put1<int32_t>(fo, (int32_t)st.attempts.size());
+	for (auto& a : st.attempts) { put1<float>(fo, a.factor); put1<float>(fo, a.slope); put1<int32_t>(fo, a.ok ? 1 : 0); }
+	put1<float>(fo, st.best_factor);
+	for (auto& c : st.bundle.component) put(fo, c.homo.data, 9);
+	st.bundle.proj_method = ConnectedImages::flat;
+	st.bundle.update_proj_range();
+	op_canvas* blended = st.blend();
+	put_canvas(fo, blended);
+	op_canvas* pano = st.perspective_correction(blended);
+	op_canvas_free(blended);
+	put(fo, st.corners, 8);
+	put(fo, st.inv, 9);
+	put_canvas(fo, pano);
+	fclose(fo);
+	int h, w;
+	PANO_HIP_CHECK(op_canvas_dims(pano, &h, &w));
+	fprintf(stderr, "Final Image Size: (%d, %d)\n", w, h);
+	if (crop) {
+		op_canvas* cc = nullptr;
+		PANO_HIP_CHECK(op_canvas_crop(HipContext::get(), pano, &cc, nullptr, nullptr));
+		op_canvas_free(pano);
+		pano = cc;
+		PANO_HIP_CHECK(op_canvas_dims(pano, &h, &w));
+		fprintf(stderr, "Cropped Image Size: (%d, %d)\n", w, h);
+	}
+	if (png_path) hip_write_png(png_path, pano);
+	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
+	op_canvas_free(pano);
+	return 0;
+}
+
+static void put_mat(FILE* fo, const Mat32f& m) {
+	put1<int32_t>(fo, m.rows()); put1<int32_t>(fo, m.cols());
+	put(fo, m.ptr(), (size_t)m.rows() * m.cols() * 3);
+}
+// CylinderStitcher::build() as a client calls it: build(), the reference's own perspective_correction(Mat32f) on the blend
+// that build left, then build_canvas(crop) on the same object for the files
+static int run_cylinder_build(CylinderStitcher& st, const char* out_path, const char* png_path, bool resident, bool crop, bool profile) {
+	st.resident_views = resident;
+	FILE* fo = fopen(out_path, "wb");
+	if (!fo) { perror(out_path); return 2; }
+	Mat32f pano = st.build();
+	put_mat(fo, pano);
+	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
+	{	// the hook for the reference's source: a blended Mat32f in, the corrected one out
+		op_canvas* blended = st.blend();
+		int h, w;
+		PANO_HIP_CHECK(op_canvas_dims(blended, &h, &w));
+		Mat32f ret(h, w, 3);
+		PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), blended, ret.ptr()));
+		op_canvas_free(blended);
+		put_mat(fo, hip_perspective_correction(st.bundle, ret));
+	}
+	op_ctx* ctx = HipContext::get();
+	if (profile) { PANO_HIP_CHECK(op_ctx_set_profiling(ctx, 1)); PANO_HIP_CHECK(op_ctx_profile_reset(ctx)); }
+	const auto t0 = std::chrono::steady_clock::now();
+	op_canvas* cv = st.build_canvas(crop);
+	PANO_HIP_CHECK(op_ctx_sync(ctx));
+	const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	if (profile) {	// the context's stages (HIP events; those labelled "(host)" are host clocks), then their sums and the call's wall time
+		double dev = 0, host = 0;
+		for (int i = 0; i < op_ctx_profile_count(ctx); ++i) {
+			const char* label; double ms; long calls;
+			PANO_HIP_CHECK(op_ctx_profile_get(ctx, i, &label, &ms, &calls));
+			fprintf(stderr, "profile: %.4f ms, %ld calls: %s\n", ms, calls, label);
+			(std::string(label).find("(host)") == std::string::npos ? dev : host) += ms;
+		}
+		fprintf(stderr, "build_canvas: %.4f ms device stages, %.4f ms host stages, %.4f ms wall\n", dev, host, wall_ms);
+		PANO_HIP_CHECK(op_ctx_set_profiling(ctx, 0));
+	}
+	put_canvas(fo, cv);
+	fclose(fo);
+	if (png_path) hip_write_png(png_path, cv);
+	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, cv, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
+	op_canvas_free(cv);
+	return 0;
+}
+
 int main(int argc, char** argv) {
 	bool gain = false;
 	int gbx = 1, gby = 1;
@@ -179,6 +295,7 @@ int main(int argc, char** argv) {
 	bool resident = false;
 	const char* jpeg_list = nullptr;
 	bool jpeg_orient = false;
+	bool crop = false, profile = false;
 	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
@@ -187,6 +304,8 @@ int main(int argc, char** argv) {
 			else if (std::string(argv[k]) == "--resident-views") resident = true;
 			else if (std::string(argv[k]) == "--jpeg-list" && k + 1 < argc) { jpeg_list = argv[++k]; resident = true; }
 			else if (std::string(argv[k]) == "--jpeg-orient") jpeg_orient = true;
+			else if (std::string(argv[k]) == "--crop") crop = true;
+			else if (std::string(argv[k]) == "--profile") profile = true;
 			else if (std::string(argv[k]) == "--png" && k + 1 < argc) png_path = argv[++k];
 			else if (std::string(argv[k]) == "--jpeg" && k + 1 < argc) g_jpeg_path = argv[++k];
 			else if (std::string(argv[k]) == "--jpeg-444") g_jpeg_444 = true;
@@ -206,15 +325,22 @@ int main(int argc, char** argv) {
 		argc = m;
 	}
 	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH [--jpeg-orient]]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build|cylinder|cylinder_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH [--jpeg-orient]] [--crop] [--profile]\n", argv[0]); return 2; }
 	if (jpeg_orient && !jpeg_list) { fprintf(stderr, "--jpeg-orient goes with --jpeg-list\n"); return 2; }
 	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	const std::string mode = argc > 4 ? argv[4] : "";
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
+	const bool cylinder_mode = mode == "cylinder" || mode == "cylinder_build";
+	if (cylinder_mode) {
+		if (gain || vig) { fprintf(stderr, "cylinder mode takes no gain or vignetting compensation\n"); return 2; }
+		config::CYLINDER = true; config::ESTIMATE_CAMERA = false; config::TRANS = false; config::ORDERED_INPUT = true;
+	}
+	if (crop && !cylinder_mode) { fprintf(stderr, "--crop goes with cylinder\n"); return 2; }
+	if (profile && mode != "cylinder_build") { fprintf(stderr, "--profile goes with cylinder_build\n"); return 2; }
 	if (jpeg_list) {
-		if (!camera_mode) { fprintf(stderr, "--jpeg-list goes with camera, camera_ordered or camera_build\n"); return 2; }
+		if (!camera_mode && !cylinder_mode) { fprintf(stderr, "--jpeg-list goes with camera, camera_ordered, camera_build or cylinder\n"); return 2; }
 		std::vector<std::string> paths;
 		FILE* fl = fopen(jpeg_list, "r");
 		if (!fl) { perror(jpeg_list); return 2; }
@@ -225,6 +351,11 @@ int main(int argc, char** argv) {
 			if (!p.empty()) paths.push_back(p);
 		}
 		fclose(fl);
+		if (cylinder_mode) {
+			CylinderStitcher st(paths, base_seed, jpeg_orient);
+			if (mode == "cylinder_build") return run_cylinder_build(st, argv[2], png_path, resident, crop, profile);
+			return run_cylinder_mode(st, argv[2], png_path, resident, crop);
+		}
 		Stitcher st(paths, base_seed, jpeg_orient);
 		if (mode == "camera_build") return run_build(st, argv[2], gain, gbx, gby, vig, png_path, resident);
 		return run_camera_mode(st, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
@@ -240,6 +371,11 @@ int main(int argc, char** argv) {
 		if (fread(mats.back().ptr(), sizeof(float), (size_t)h * w * 3, fi) != (size_t)h * w * 3) return 2;
 	}
 	fclose(fi);
+	if (cylinder_mode) {
+		CylinderStitcher st(mats, base_seed);
+		if (mode == "cylinder_build") return run_cylinder_build(st, argv[2], png_path, resident, crop, profile);
+		return run_cylinder_mode(st, argv[2], png_path, resident, crop);
+	}
 	if (camera_mode) {
 		Stitcher st(mats, base_seed);
 		if (mode == "camera_build") return run_build(st, argv[2], gain, gbx, gby, vig, png_path, resident);
