@@ -21,6 +21,12 @@
 //   CylinderWarper::warp                                  stitch/warp.hh:47-55
 // Error behaviour follows the reference: unrecoverable conditions end in error_exit()
 // (lib/debugutils.cc:57-60: message on stderr, exit(1)); no exception crosses the C-ABI.
+//
+// Layout, top down: errors, config snapshot, HipContext; the owning handles (HipFeatures .. HipJpeg: std::unique_ptr with the C
+// entry's op_*_free as deleter, filled through hip_out); the helpers the adapters share, one copy of each (flattening, default
+// task list, file reading, canvas -> Mat32f, crop in place; next to the blend: bundle / component geometry and
+// hip_compensate_and_blend); the adapters in pipeline order (SIFT, MATCH, RANSAC, WARP + BLEND, the file writers); and, standalone
+// only, HipStitcherBase with HipStitcher and HipCylinderStitcher derived from it.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -128,11 +134,107 @@ class HipContext {
 		~HipContext() { op_ctx_destroy(ctx); }
 };
 
+// ---- owning handles: what a C entry handed out, released through that entry's op_*_free when its owner goes.  Functions
+// that hand a handle on to their caller return the raw pointer (release()) ----
+template <typename T, void (*Free)(T*)>
+struct HipFree { void operator()(T* p) const { Free(p); } };
+template <typename T, void (*Free)(T*)>
+using HipHandle = std::unique_ptr<T, HipFree<T, Free>>;
+using HipFeatures = HipHandle<op_features, op_features_free>;
+using HipViews = HipHandle<op_views, op_views_free>;
+using HipMatches = HipHandle<op_matches, op_matches_free>;
+using HipRansac = HipHandle<op_ransac_result, op_ransac_free>;
+using HipCanvas = HipHandle<op_canvas, op_canvas_free>;
+using HipPng = HipHandle<op_png, op_png_free>;
+using HipJpeg = HipHandle<op_jpeg, op_jpeg_free>;
+// hip_out(h): the T** a C entry writes its result through; h adopts what was written when the call's statement ends
+template <typename H>
+struct HipOut {
+	H& h;
+	typename H::pointer p = nullptr;
+	operator typename H::pointer*() { return &p; }
+	~HipOut() { h.reset(p); }
+};
+template <typename H> inline HipOut<H> hip_out(H& h) { return {h}; }
+
+// ---- the lists the C-ABI takes flat ----
+// Vec2D list <-> x, y doubles
+inline std::vector<double> hip_flatten(const std::vector<Vec2D>& pts) {
+	std::vector<double> p(pts.size() * 2 + 2);
+	for (size_t i = 0; i < pts.size(); ++i) { p[2 * i] = pts[i].x; p[2 * i + 1] = pts[i].y; }
+	return p;
+}
+inline void hip_unflatten(const std::vector<double>& p, std::vector<Vec2D>& pts) {
+	for (size_t i = 0; i < pts.size(); ++i) pts[i] = Vec2D(p[2 * i], p[2 * i + 1]);
+}
+// (i, j) pairs -> i, j ints; shapes -> w, h ints
+inline std::vector<int> hip_flatten(const std::vector<std::pair<int, int>>& pairs) {
+	std::vector<int> pr;
+	for (auto& t : pairs) { pr.push_back(t.first); pr.push_back(t.second); }
+	return pr;
+}
+inline std::vector<int> hip_flatten(const std::vector<Shape2D>& shapes) {
+	std::vector<int> sh;
+	for (auto& s : shapes) { sh.push_back(s.w); sh.push_back(s.h); }
+	return sh;
+}
+// the coordinates of a descriptor list (StitcherBase::keypoints, stitcherbase.cc:23-25)
+inline std::vector<Vec2D> hip_keypoints(const std::vector<Descriptor>& feats) {
+	std::vector<Vec2D> kps;
+	kps.reserve(feats.size());
+	for (auto& d : feats) kps.emplace_back(d.coor);
+	return kps;
+}
+// coordinates-only features (no descriptors: RANSAC reads nothing else) from one keypoint list per view
+inline HipFeatures hip_features_from_keypoints(op_ctx* ctx, const std::vector<const std::vector<Vec2D>*>& kpts) {
+	std::vector<std::vector<double>> flat;
+	std::vector<const double*> cp; std::vector<int> counts;
+	for (auto* k : kpts) { flat.push_back(hip_flatten(*k)); counts.push_back((int)k->size()); }
+	for (auto& f : flat) cp.push_back(f.data());
+	HipFeatures f;
+	PANO_HIP_CHECK(op_features_from_host(ctx, nullptr, cp.data(), counts.data(), (int)kpts.size(), hip_out(f)));
+	return f;
+}
+// the default task list of Stitcher::pairwise_match (all i < j, stitcher.cc:99-100) or, for an ordered input, of
+// linear_pairwise_match ((i, i + 1 mod n), stitcher.cc:121-124)
+inline std::vector<std::pair<int, int>> hip_default_tasks(int n, bool ordered) {
+	std::vector<std::pair<int, int>> tasks;
+	if (ordered) for (int i = 0; i < n; ++i) tasks.emplace_back(i, (i + 1) % n);
+	else for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) tasks.emplace_back(i, j);
+	return tasks;
+}
+// the bytes of a file, all of them or the first `limit`; a file that cannot be opened ends the program like read_img
+// (lib/imgio.cc:68-69)
+inline std::vector<unsigned char> hip_read_file(const std::string& path, size_t limit = (size_t)-1) {
+	FILE* f = fopen(path.c_str(), "rb");
+	if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", path.c_str()); exit(1); }
+	std::vector<unsigned char> data;
+	unsigned char buf[65536]; size_t n;
+	data.reserve(std::min(sizeof buf, limit));      // data() of an empty file is not NULL either
+	while (data.size() < limit && (n = fread(buf, 1, std::min(sizeof buf, limit - data.size()), f)) > 0) data.insert(data.end(), buf, buf + n);
+	fclose(f);
+	return data;
+}
+
+// ---- canvases ----
+// the pixels of a device canvas as a matrix in host memory; the canvas is released
+inline Mat32f hip_canvas_to_mat(HipCanvas cv) {
+	int h, w;
+	PANO_HIP_CHECK(op_canvas_dims(cv.get(), &h, &w));
+	Mat32f out(h, w, 3);
+	PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), cv.get(), out.ptr()));
+	cv.reset();     // here, not where the caller's full expression ends
+	return out;
+}
+// crop() (lib/imgproc.cc:200-235) on the device: cv becomes its largest valid rectangle, the uncropped canvas is released
+inline void hip_crop_in_place(HipCanvas& cv) {
+	HipCanvas cropped;
+	PANO_HIP_CHECK(op_canvas_crop(HipContext::get(), cv.get(), hip_out(cropped), nullptr, nullptr));
+	cv = std::move(cropped);
+}
+
 // ===================================== SIFT =====================================
-#ifdef OPENPANO_WITH_REFERENCE
-#define PANO_DETECTOR_BASE : public FeatureDetector
-#define PANO_OVERRIDE override
-#else
+#ifndef OPENPANO_WITH_REFERENCE
 // the reference's base class (feature/feature.hh:42-52): detect_feature re-centres the [0,1)
 // coordinates do_detect_feature returns (feature/feature.cc:20-28)
 class FeatureDetector {
@@ -151,42 +253,33 @@ class FeatureDetector {
 		}
 		virtual std::vector<Descriptor> do_detect_feature(const Mat32f& img) const = 0;
 };
-#define PANO_DETECTOR_BASE : public FeatureDetector
-#define PANO_OVERRIDE override
 #endif
 
 // device-resident features of a whole image set: what StitcherBase keeps as `feats`, plus the
 // op_features handle so that the matcher does not re-upload descriptors
 struct HipFeatureSet {
-	op_features* handle = nullptr;
+	HipFeatures handle;
 	// the images themselves, resident on the device in the type they were uploaded in (calc_feature with resident_views):
 	// the blend and the overlap passes read them there instead of a second, fp32 upload (ConnectedImages::views)
-	op_views* views = nullptr;
+	HipViews views;
 	std::vector<std::vector<Descriptor>> feats;     // centred coordinates, like StitcherBase::feats
 	HipFeatureSet() = default;
-	HipFeatureSet(const HipFeatureSet&) = delete;
-	HipFeatureSet& operator=(const HipFeatureSet&) = delete;
-	HipFeatureSet(HipFeatureSet&& o): handle(o.handle), views(o.views), feats(std::move(o.feats)) { o.handle = nullptr; o.views = nullptr; }
-	HipFeatureSet& operator=(HipFeatureSet&& o) {
-		if (this != &o) {
-			op_features_free(handle); op_views_free(views);
-			handle = o.handle; views = o.views; feats = std::move(o.feats); o.handle = nullptr; o.views = nullptr;
-		}
-		return *this;
-	}
-	~HipFeatureSet() { op_features_free(handle); op_views_free(views); }
+	HipFeatureSet(HipFeatureSet&&) = default;
+	HipFeatureSet& operator=(HipFeatureSet&&) = default;
+	~HipFeatureSet() { handle.reset(); }            // the features go before the views, as in a move assignment
 };
 
-class HipSIFTDetector PANO_DETECTOR_BASE {
+class HipSIFTDetector : public FeatureDetector {
 	public:
 		// SIFTDetector::do_detect_feature (feature/feature.cc:31-47): [0,1) coordinates
-		std::vector<Descriptor> do_detect_feature(const Mat32f& mat) const PANO_OVERRIDE {
+		std::vector<Descriptor> do_detect_feature(const Mat32f& mat) const override {
 			op_ctx* ctx = HipContext::get();
 			const op_config cfg = hip_config_snapshot();
 			op_image im{mat.ptr(), mat.rows(), mat.cols(), 0, OP_F32};
 			if (mat.channels() != 3) { fprintf(stderr, "HipSIFTDetector: image must have 3 channels\n"); exit(1); }
-			op_features* f = nullptr;
-			PANO_HIP_CHECK(op_sift_batch(ctx, &cfg, &im, 1, &f));
+			HipFeatures own;
+			PANO_HIP_CHECK(op_sift_batch(ctx, &cfg, &im, 1, hip_out(own)));
+			const op_features* f = own.get();
 			const int k = op_features_count(f, 0);
 			std::vector<float> desc((size_t)k * 128);
 			std::vector<double> real((size_t)k * 2);
@@ -194,7 +287,7 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 				PANO_HIP_CHECK(op_features_copy(ctx, f, 0, desc.data(), nullptr));
 				PANO_HIP_CHECK(op_features_copy_real(ctx, f, 0, real.data()));
 			}
-			op_features_free(f);
+			own.reset();
 			std::vector<Descriptor> ret(k);
 			for (int i = 0; i < k; ++i) {
 				ret[i].coor = Vec2D(real[2 * i], real[2 * i + 1]);
@@ -213,8 +306,6 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 			const op_config cfg = hip_config_snapshot();
 			std::vector<op_image> ims;
 			for (auto* m : imgs) ims.push_back(op_image{m->ptr(), m->rows(), m->cols(), 0, OP_F32});
-			HipFeatureSet fs;
-			std::vector<float> desc; std::vector<double> coor;
 			// Images that came out of a decoder are bytes / 255 (read_img, lib/imgio.cc:54-56,75-77: (float)((double)byte / 255.0)).
 			// When EVERY value of every image is exactly such a float, the bytes travel instead -- a quarter of the PCIe traffic,
 			// pageable memory at that -- and the device converts them with the same expression (OP_U8): the same features, bit for bit.
@@ -257,37 +348,28 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 				if (all_bytes.load()) for (size_t k = 0; k < imgs.size(); ++k) { ims[k].data = bytes[k].get(); ims[k].dtype = OP_U8; }
 			}
 			if (op_group* g = HipContext::group()) {        // images dealt over the group's GPUs, features all-gathered
-				PANO_HIP_CHECK(op_sift_batch_multi(g, &cfg, ims.data(), (int)ims.size(), &fs.handle));
-				ctx = op_group_ctx(g, 0);
-				const size_t total = (size_t)op_features_total(fs.handle);
-				desc.resize(total * 128 + 1); coor.resize(total * 2 + 1);
-				for (size_t k = 0; k < imgs.size(); ++k)
-					if (op_features_count(fs.handle, (int)k))
-						PANO_HIP_CHECK(op_features_copy(ctx, fs.handle, (int)k, desc.data() + (size_t)op_features_offset(fs.handle, (int)k) * 128,
-								coor.data() + (size_t)op_features_offset(fs.handle, (int)k) * 2));
-			} else if (resident_views) {
-				PANO_HIP_CHECK(op_views_upload(ctx, ims.data(), (int)ims.size(), &fs.views));
-				std::vector<op_image> dev(ims.size());
-				for (size_t k = 0; k < ims.size(); ++k) PANO_HIP_CHECK(op_views_image(fs.views, (int)k, &dev[k]));
-				PANO_HIP_CHECK(op_sift_batch(ctx, &cfg, dev.data(), (int)dev.size(), &fs.handle));
-				const size_t total = (size_t)op_features_total(fs.handle);
-				desc.resize(total * 128 + 1); coor.resize(total * 2 + 1);
-				for (size_t k = 0; k < imgs.size(); ++k)
-					if (op_features_count(fs.handle, (int)k))
-						PANO_HIP_CHECK(op_features_copy(ctx, fs.handle, (int)k, desc.data() + (size_t)op_features_offset(fs.handle, (int)k) * 128,
-								coor.data() + (size_t)op_features_offset(fs.handle, (int)k) * 2));
-			} else {
-				// uploads, kernels and the copy back to the host pipelined over chunks of the batch; the host buffers are
-				// sized from a first guess and the call repeated once if the images hold more features than that
-				size_t cap = (size_t)imgs.size() * 4096;
-				for (int attempt = 0; attempt < 2; ++attempt) {
-					desc.resize(cap * 128 + 1); coor.resize(cap * 2 + 1);
-					const int rc = op_sift_batch_host(ctx, &cfg, ims.data(), (int)ims.size(), desc.data(), coor.data(), (int64_t)cap, &fs.handle);
-					if (rc == OP_OK) break;
-					if (rc != OP_ERR_CAPACITY || attempt == 1) hip_error_exit("op_sift_batch_host");
-					cap = (size_t)op_features_total(fs.handle) + 16;
-					op_features_free(fs.handle); fs.handle = nullptr;
-				}
+				HipFeatureSet fs;
+				PANO_HIP_CHECK(op_sift_batch_multi(g, &cfg, ims.data(), (int)ims.size(), hip_out(fs.handle)));
+				fetch_feats(op_group_ctx(g, 0), fs, imgs.size());
+				return fs;
+			}
+			if (resident_views) {       // one upload, then as for views that are on the device already
+				HipViews views;
+				PANO_HIP_CHECK(op_views_upload(ctx, ims.data(), (int)ims.size(), hip_out(views)));
+				return calc_feature(views.release());
+			}
+			// uploads, kernels and the copy back to the host pipelined over chunks of the batch; the host buffers are
+			// sized from a first guess and the call repeated once if the images hold more features than that
+			HipFeatureSet fs;
+			std::vector<float> desc; std::vector<double> coor;
+			size_t cap = (size_t)imgs.size() * 4096;
+			for (int attempt = 0; attempt < 2; ++attempt) {
+				desc.resize(cap * 128 + 1); coor.resize(cap * 2 + 1);
+				const int rc = op_sift_batch_host(ctx, &cfg, ims.data(), (int)ims.size(), desc.data(), coor.data(), (int64_t)cap, hip_out(fs.handle));
+				if (rc == OP_OK) break;
+				if (rc != OP_ERR_CAPACITY || attempt == 1) hip_error_exit("op_sift_batch_host");
+				cap = (size_t)op_features_total(fs.handle.get()) + 16;
+				fs.handle.reset();
 			}
 			fill_feats(fs, imgs.size(), desc, coor);
 			return fs;
@@ -299,33 +381,38 @@ class HipSIFTDetector PANO_DETECTOR_BASE {
 			op_ctx* ctx = HipContext::get();
 			const op_config cfg = hip_config_snapshot();
 			HipFeatureSet fs;
-			fs.views = views;
+			fs.views.reset(views);
 			const int n = op_views_count(views);
 			if (n <= 0) hip_error_exit("calc_feature(op_views*)");
 			std::vector<op_image> dev((size_t)n);
 			for (int k = 0; k < n; ++k) PANO_HIP_CHECK(op_views_image(views, k, &dev[k]));
-			PANO_HIP_CHECK(op_sift_batch(ctx, &cfg, dev.data(), n, &fs.handle));
-			const size_t total = (size_t)op_features_total(fs.handle);
-			std::vector<float> desc(total * 128 + 1); std::vector<double> coor(total * 2 + 1);
-			for (int k = 0; k < n; ++k)
-				if (op_features_count(fs.handle, k))
-					PANO_HIP_CHECK(op_features_copy(ctx, fs.handle, k, desc.data() + (size_t)op_features_offset(fs.handle, k) * 128,
-							coor.data() + (size_t)op_features_offset(fs.handle, k) * 2));
-			fill_feats(fs, (size_t)n, desc, coor);
+			PANO_HIP_CHECK(op_sift_batch(ctx, &cfg, dev.data(), n, hip_out(fs.handle)));
+			fetch_feats(ctx, fs, (size_t)n);
 			return fs;
 		}
 
 	private:
+		// every image's descriptors and coordinates from the device handle into fs.feats
+		static void fetch_feats(op_ctx* ctx, HipFeatureSet& fs, size_t nimg) {
+			const op_features* f = fs.handle.get();
+			const size_t total = (size_t)op_features_total(f);
+			std::vector<float> desc(total * 128 + 1); std::vector<double> coor(total * 2 + 1);
+			for (int k = 0; k < (int)nimg; ++k)
+				if (op_features_count(f, k))
+					PANO_HIP_CHECK(op_features_copy(ctx, f, k, desc.data() + (size_t)op_features_offset(f, k) * 128, coor.data() + (size_t)op_features_offset(f, k) * 2));
+			fill_feats(fs, nimg, desc, coor);
+		}
 		static void fill_feats(HipFeatureSet& fs, size_t nimg, const std::vector<float>& desc, const std::vector<double>& coor) {
+			const op_features* f = fs.handle.get();
 			fs.feats.resize(nimg);
 			for (size_t k = 0; k < nimg; ++k) {
-				const int n = op_features_count(fs.handle, (int)k);
+				const int n = op_features_count(f, (int)k);
 				if (n == 0) {    // stitcherbase.cc:20-21
 					fprintf(stderr, "Cannot find feature in image %d!\n", (int)k);
 					exit(1);
 				}
-				const float* d = desc.data() + (size_t)op_features_offset(fs.handle, (int)k) * 128;
-				const double* c = coor.data() + (size_t)op_features_offset(fs.handle, (int)k) * 2;
+				const float* d = desc.data() + (size_t)op_features_offset(f, (int)k) * 128;
+				const double* c = coor.data() + (size_t)op_features_offset(f, (int)k) * 2;
 				fs.feats[k].resize(n);
 				for (int i = 0; i < n; ++i) {
 					fs.feats[k][i].coor = Vec2D(c[2 * i], c[2 * i + 1]);
@@ -347,12 +434,8 @@ inline op_views* hip_read_jpeg_views(op_ctx* ctx, const std::vector<std::string>
 	std::vector<const unsigned char*> ptr(paths.size());
 	std::vector<int64_t> size(paths.size());
 	for (size_t k = 0; k < paths.size(); ++k) {
-		FILE* f = fopen(paths[k].c_str(), "rb");
-		if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", paths[k].c_str()); exit(1); }      // lib/imgio.cc:68-69
-		unsigned char buf[65536]; size_t n;
-		while ((n = fread(buf, 1, sizeof buf, f)) > 0) data[k].insert(data[k].end(), buf, buf + n);
-		fclose(f);
-		ptr[k] = data[k].data(); size[k] = (int64_t)data[k].size();
+		data[k] = hip_read_file(paths[k]);
+		ptr[k] = data[k].empty() ? nullptr : data[k].data(); size[k] = (int64_t)data[k].size();     // an empty file is refused as NULL data
 	}
 	op_views* v = nullptr;
 	if (orient) PANO_HIP_CHECK(op_views_decode_jpeg_oriented(ctx, ptr.data(), size.data(), (int)paths.size(), nullptr, &v));
@@ -364,11 +447,7 @@ inline op_views* hip_read_jpeg_views(op_ctx* ctx, const std::vector<std::string>
 // (op_jpeg_exif) -- the latter is what config.cfg's FOCAL_LENGTH asks the user for.  Either pointer may be NULL.  EXIF sits in
 // front of the tables, so the first megabyte of the file is all that is read.
 inline void hip_jpeg_exif(const std::string& path, int* orientation, int* focal35) {
-	FILE* f = fopen(path.c_str(), "rb");
-	if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", path.c_str()); exit(1); }      // lib/imgio.cc:68-69
-	std::vector<unsigned char> head(1 << 20);
-	head.resize(fread(head.data(), 1, head.size(), f));
-	fclose(f);
+	const std::vector<unsigned char> head = hip_read_file(path, 1 << 20);
 	PANO_HIP_CHECK(op_jpeg_exif(head.data(), (int64_t)head.size(), orientation, focal35));
 }
 
@@ -383,7 +462,7 @@ class HipPairWiseMatcher {
 			upload();
 		}
 		// descriptors already resident (HipSIFTDetector::calc_feature): no second H2D pass
-		explicit HipPairWiseMatcher(const HipFeatureSet& fs): feats(fs.feats), handle(fs.handle), owns(false) {}
+		explicit HipPairWiseMatcher(const HipFeatureSet& fs): feats(fs.feats), handle(fs.handle.get()), owns(false) {}
 		HipPairWiseMatcher(const HipPairWiseMatcher&) = delete;
 		HipPairWiseMatcher& operator=(const HipPairWiseMatcher&) = delete;
 		~HipPairWiseMatcher() { if (owns) op_features_free(handle); }
@@ -421,33 +500,27 @@ class HipPairWiseMatcher {
 			std::vector<const float*> dp(n); std::vector<const double*> cp(n); std::vector<int> counts(n);
 			for (int k = 0; k < n; ++k) {       // PairWiseMatcher::build flattening (matcher.cc:75-81)
 				counts[k] = (int)feats[k].size();
-				flat[k].resize((size_t)counts[k] * 128 + 1); coor[k].resize((size_t)counts[k] * 2 + 1);
+				flat[k].resize((size_t)counts[k] * 128 + 1);
 				for (int i = 0; i < counts[k]; ++i) {
 					if (feats[k][i].descriptor.size() != 128) { fprintf(stderr, "PairWiseMatcher: descriptors must be 128-D\n"); exit(1); }
 					memcpy(&flat[k][(size_t)i * 128], feats[k][i].descriptor.data(), 128 * sizeof(float));
-					coor[k][2 * i] = feats[k][i].coor.x; coor[k][2 * i + 1] = feats[k][i].coor.y;
 				}
+				coor[k] = hip_flatten(hip_keypoints(feats[k]));
 				dp[k] = flat[k].data(); cp[k] = coor[k].data();
 			}
 			PANO_HIP_CHECK(op_features_from_host(HipContext::home(), dp.data(), cp.data(), counts.data(), n, &handle));
 		}
-		void precompute_default() const {
-			const int n = (int)feats.size();
-			std::vector<std::pair<int, int>> tasks;
-			if (config::ORDERED_INPUT) for (int i = 0; i < n; ++i) tasks.emplace_back(i, (i + 1) % n);   // stitcher.cc:121-124
-			else for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) tasks.emplace_back(i, j);    // stitcher.cc:99-100
-			run(tasks);
-		}
+		void precompute_default() const { run(hip_default_tasks((int)feats.size(), config::ORDERED_INPUT)); }
 		void run(const std::vector<std::pair<int, int>>& tasks) const {
 			if (tasks.empty()) return;
-			std::vector<int> pr;
-			for (auto& t : tasks) { pr.push_back(t.first); pr.push_back(t.second); }
+			const std::vector<int> pr = hip_flatten(tasks);
 			const op_config cfg = hip_config_snapshot();
-			op_matches* m = nullptr;
+			HipMatches own;
 			if (op_group* g = HipContext::group())          // pair list dealt over the group's GPUs (K_i * K_j balanced)
-				PANO_HIP_CHECK(op_match_pairs_multi(g, &cfg, handle, pr.data(), (int)tasks.size(), &m));
+				PANO_HIP_CHECK(op_match_pairs_multi(g, &cfg, handle, pr.data(), (int)tasks.size(), hip_out(own)));
 			else
-				PANO_HIP_CHECK(op_match_pairs(HipContext::get(), &cfg, handle, pr.data(), (int)tasks.size(), &m));
+				PANO_HIP_CHECK(op_match_pairs(HipContext::get(), &cfg, handle, pr.data(), (int)tasks.size(), hip_out(own)));
+			const op_matches* m = own.get();
 			for (size_t p = 0; p < tasks.size(); ++p) {
 				const int c = op_matches_count(m, (int)p);
 				std::vector<int> idx((size_t)c * 2 + 2);
@@ -456,7 +529,6 @@ class HipPairWiseMatcher {
 				for (int q = 0; q < c; ++q) md.data.emplace_back(idx[2 * q], idx[2 * q + 1]);
 				cache[tasks[p]] = std::move(md);
 			}
-			op_matches_free(m);
 		}
 };
 
@@ -480,27 +552,19 @@ class HipTransformEstimation {
 		bool get_transform(MatchInfo* info) {
 			op_ctx* ctx = HipContext::get();
 			const op_config cfg = hip_config_snapshot();
-			std::vector<double> c1(kp1.size() * 2 + 2), c2(kp2.size() * 2 + 2);
-			for (size_t i = 0; i < kp1.size(); ++i) { c1[2 * i] = kp1[i].x; c1[2 * i + 1] = kp1[i].y; }
-			for (size_t i = 0; i < kp2.size(); ++i) { c2[2 * i] = kp2[i].x; c2[2 * i + 1] = kp2[i].y; }
-			const double* cp[2] = {c1.data(), c2.data()};
-			const int counts[2] = {(int)kp1.size(), (int)kp2.size()};
-			op_features* f = nullptr;
-			PANO_HIP_CHECK(op_features_from_host(ctx, nullptr, cp, counts, 2, &f));
-			std::vector<int> idx(match.data.size() * 2 + 2);
-			for (size_t i = 0; i < match.data.size(); ++i) { idx[2 * i] = match.data[i].first; idx[2 * i + 1] = match.data[i].second; }
+			const HipFeatures f = hip_features_from_keypoints(ctx, {&kp1, &kp2});
+			std::vector<int> idx = hip_flatten(match.data);
+			idx.resize(idx.size() + 2);
 			const int* ip[1] = {idx.data()};
 			const int mc[1] = {(int)match.data.size()};
-			op_matches* m = nullptr;
-			PANO_HIP_CHECK(op_matches_from_host(ip, mc, 1, &m));
+			HipMatches m;
+			PANO_HIP_CHECK(op_matches_from_host(ip, mc, 1, hip_out(m)));
 			const int pairs[2] = {0, 1};
 			const int shapes[4] = {shape1.w, shape1.h, shape2.w, shape2.h};
 			uint32_t seed = seed_injected() ? injected_seed() : std::random_device{}();
-			op_ransac_result* r = nullptr;
-			PANO_HIP_CHECK(op_ransac_pairs(ctx, &cfg, f, m, pairs, 1, shapes, &seed, 0, &r));
-			const bool ok = fill(r, 0, match, kp1, kp2, info);
-			op_ransac_free(r); op_matches_free(m); op_features_free(f);
-			return ok;
+			HipRansac r;
+			PANO_HIP_CHECK(op_ransac_pairs(ctx, &cfg, f.get(), m.get(), pairs, 1, shapes, &seed, 0, hip_out(r)));
+			return fill(r.get(), 0, match, kp1, kp2, info);
 		}
 
 		// MatchInfo of pair p of a batched result (fill_inliers_to_matchinfo's outputs,
@@ -534,32 +598,31 @@ inline void hip_match_and_estimate(const HipFeatureSet& fs, const std::vector<Sh
 		const std::vector<uint32_t>& seeds, uint32_t base_seed, std::vector<MatchData>& matches, std::vector<std::pair<bool, MatchInfo>>& out) {
 	op_ctx* ctx = HipContext::get();
 	const op_config cfg = hip_config_snapshot();
-	std::vector<int> pr, sh;
-	for (auto& t : tasks) { pr.push_back(t.first); pr.push_back(t.second); }
-	for (auto& s : shapes) { sh.push_back(s.w); sh.push_back(s.h); }
-	op_matches* m = nullptr;
-	op_ransac_result* r = nullptr;
+	const std::vector<int> pr = hip_flatten(tasks), sh = hip_flatten(shapes);
+	const op_features* f = fs.handle.get();
+	const uint32_t* sd = seeds.empty() ? nullptr : seeds.data();
+	HipMatches m;
+	HipRansac r;
 	if (op_group* g = HipContext::group()) {           // pair list dealt over the group's GPUs; RANSAC follows the deal
-		PANO_HIP_CHECK(op_match_pairs_multi(g, &cfg, fs.handle, pr.data(), (int)tasks.size(), &m));
-		PANO_HIP_CHECK(op_ransac_pairs_multi(g, &cfg, fs.handle, m, pr.data(), (int)tasks.size(), sh.data(), seeds.empty() ? nullptr : seeds.data(), base_seed, &r));
+		PANO_HIP_CHECK(op_match_pairs_multi(g, &cfg, f, pr.data(), (int)tasks.size(), hip_out(m)));
+		PANO_HIP_CHECK(op_ransac_pairs_multi(g, &cfg, f, m.get(), pr.data(), (int)tasks.size(), sh.data(), sd, base_seed, hip_out(r)));
 	} else {
-		PANO_HIP_CHECK(op_match_pairs(ctx, &cfg, fs.handle, pr.data(), (int)tasks.size(), &m));
-		PANO_HIP_CHECK(op_ransac_pairs(ctx, &cfg, fs.handle, m, pr.data(), (int)tasks.size(), sh.data(), seeds.empty() ? nullptr : seeds.data(), base_seed, &r));
+		PANO_HIP_CHECK(op_match_pairs(ctx, &cfg, f, pr.data(), (int)tasks.size(), hip_out(m)));
+		PANO_HIP_CHECK(op_ransac_pairs(ctx, &cfg, f, m.get(), pr.data(), (int)tasks.size(), sh.data(), sd, base_seed, hip_out(r)));
 	}
 	std::vector<int64_t> off(tasks.size() + 1);
-	std::vector<int> idx((size_t)op_matches_total(m) * 2 + 2);
-	PANO_HIP_CHECK(op_matches_copy_all(m, idx.data(), off.data()));
+	std::vector<int> idx((size_t)op_matches_total(m.get()) * 2 + 2);
+	PANO_HIP_CHECK(op_matches_copy_all(m.get(), idx.data(), off.data()));
 	matches.assign(tasks.size(), MatchData());
 	out.assign(tasks.size(), std::pair<bool, MatchInfo>());
-	std::vector<std::vector<Vec2D>> kps(fs.feats.size());
-	for (size_t k = 0; k < fs.feats.size(); ++k) { kps[k].reserve(fs.feats[k].size()); for (auto& d : fs.feats[k]) kps[k].push_back(d.coor); }
+	std::vector<std::vector<Vec2D>> kps;
+	for (auto& fk : fs.feats) kps.push_back(hip_keypoints(fk));
 	for (size_t p = 0; p < tasks.size(); ++p) {
 		MatchData& md = matches[p];
 		md.data.reserve((size_t)(off[p + 1] - off[p]));
 		for (int64_t q = off[p]; q < off[p + 1]; ++q) md.data.emplace_back(idx[2 * q], idx[2 * q + 1]);
-		out[p].first = HipTransformEstimation::fill(r, (int)p, md, kps[tasks[p].first], kps[tasks[p].second], &out[p].second);
+		out[p].first = HipTransformEstimation::fill(r.get(), (int)p, md, kps[tasks[p].first], kps[tasks[p].second], &out[p].second);
 	}
-	op_ransac_free(r); op_matches_free(m);
 }
 
 // ---- the batched hooks inside the reference's OWN loops ("batched form") ----
@@ -578,10 +641,7 @@ class HipBatchedMatcher {
 	public:
 		// imgs: anything with shape() per image (std::vector<ImageRef>, stitcherbase.hh:28)
 		template <typename ImageList>
-		HipBatchedMatcher(const HipFeatureSet& fs, const ImageList& imgs) {
-			const int n = (int)fs.feats.size();
-			if (config::ORDERED_INPUT) for (int i = 0; i < n; ++i) tasks.emplace_back(i, (i + 1) % n);         // stitcher.cc:121-124
-			else for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) tasks.emplace_back(i, j);          // stitcher.cc:99-100
+		HipBatchedMatcher(const HipFeatureSet& fs, const ImageList& imgs): tasks(hip_default_tasks((int)fs.feats.size(), config::ORDERED_INPUT)) {
 			std::vector<Shape2D> shapes;
 			for (auto& r : imgs) shapes.push_back(r.shape());
 			// the reference seeds every get_transform from std::random_device (transform_estimate.cc:64-65)
@@ -701,14 +761,24 @@ inline op_blend_geom hip_blend_prepare(const Bundle& b, std::vector<double>& hin
 // the bundle's resident views, when it has the member (the reference's ConnectedImages has none)
 template <typename Bundle> inline auto hip_bundle_views(const Bundle& b, int) -> decltype(b.views) { return b.views; }
 template <typename Bundle> inline const op_views* hip_bundle_views(const Bundle&, long) { return nullptr; }
+// the bundle's projection, range and resolution as the C-ABI's op_blend_geom; a component's homo_inv and range into its op_blend_image
 template <typename Bundle>
-inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_geom& g) {
-	const int n = (int)b.component.size();
+inline void hip_bundle_geom(const Bundle& b, op_blend_geom& g) {
 	const Vec2D res = b.get_final_resolution();
 	g.proj_method = (int)b.proj_method;
 	g.proj_min[0] = b.proj_range.min.x; g.proj_min[1] = b.proj_range.min.y;
 	g.proj_max[0] = b.proj_range.max.x; g.proj_max[1] = b.proj_range.max.y;
 	g.resolution[0] = res.x; g.resolution[1] = res.y;
+}
+template <typename Component>
+inline void hip_component_geom(const Component& c, op_blend_image& im) {
+	for (int k = 0; k < 9; ++k) im.homo_inv[k] = c.homo_inv[k];
+	im.range[0] = c.range.min.x; im.range[1] = c.range.min.y; im.range[2] = c.range.max.x; im.range[3] = c.range.max.y;
+}
+template <typename Bundle>
+inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_geom& g) {
+	const int n = (int)b.component.size();
+	hip_bundle_geom(b, g);
 	std::vector<op_blend_image> ims(n);
 	const op_views* views = hip_bundle_views(b, 0);
 	if (views && op_views_count(views) != n) { fprintf(stderr, "hip_blend_images: %d resident views for %d components\n", op_views_count(views), n); exit(1); }
@@ -731,8 +801,7 @@ inline std::vector<op_blend_image> hip_blend_images(const Bundle& b, op_blend_ge
 			}
 		}
 		if (!ims[i].data) { fprintf(stderr, "hip_blend_images: resident view %d is %d x %d, its component %d x %d\n", i, ims[i].mat_w, ims[i].mat_h, ims[i].w, ims[i].h); exit(1); }
-		for (int k = 0; k < 9; ++k) ims[i].homo_inv[k] = c.homo_inv[k];
-		ims[i].range[0] = c.range.min.x; ims[i].range[1] = c.range.min.y; ims[i].range[2] = c.range.max.x; ims[i].range[3] = c.range.max.y;
+		hip_component_geom(c, ims[i]);
 	}
 	return ims;
 }
@@ -814,23 +883,13 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 	const std::vector<op_blend_image> ims = hip_blend_images(b, g);
 	const size_t per_image = bx > 0 ? (size_t)3 * bx * by : 3;
 	if (!gains.empty() && gains.size() != per_image * n) { fprintf(stderr, "hip_blend: %zu gains for %d images\n", gains.size(), n); exit(1); }
-	op_canvas* cv = nullptr;
-	if (poly) PANO_HIP_CHECK(op_blend_vignette(ctx, &cfg, &g, ims.data(), n, gains.empty() ? nullptr : gains.data(), poly, &cv));
-	else if (gains.empty()) PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
-	else if (bx > 0) PANO_HIP_CHECK(op_blend_block_gains(ctx, &cfg, &g, ims.data(), n, bx, by, gains.data(), &cv));
-	else PANO_HIP_CHECK(op_blend_gains(ctx, &cfg, &g, ims.data(), n, gains.data(), &cv));
-	if (crop) {
-		op_canvas* cc = nullptr;
-		PANO_HIP_CHECK(op_canvas_crop(ctx, cv, &cc, nullptr, nullptr));
-		op_canvas_free(cv);
-		cv = cc;
-	}
-	int h, w;
-	PANO_HIP_CHECK(op_canvas_dims(cv, &h, &w));
-	Mat32f out(h, w, 3);
-	PANO_HIP_CHECK(op_canvas_copy(ctx, cv, out.ptr()));
-	op_canvas_free(cv);
-	return out;
+	HipCanvas cv;
+	if (poly) PANO_HIP_CHECK(op_blend_vignette(ctx, &cfg, &g, ims.data(), n, gains.empty() ? nullptr : gains.data(), poly, hip_out(cv)));
+	else if (gains.empty()) PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, hip_out(cv)));
+	else if (bx > 0) PANO_HIP_CHECK(op_blend_block_gains(ctx, &cfg, &g, ims.data(), n, bx, by, gains.data(), hip_out(cv)));
+	else PANO_HIP_CHECK(op_blend_gains(ctx, &cfg, &g, ims.data(), n, gains.data(), hip_out(cv)));
+	if (crop) hip_crop_in_place(cv);
+	return hip_canvas_to_mat(std::move(cv));
 }
 
 // gains: empty = op_blend, else n x 3 exposure gains (op_blend_gains)
@@ -844,16 +903,42 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 template <typename Bundle>
 inline Mat32f hip_blend(const Bundle& b, bool crop = false) { return hip_blend(b, crop, std::vector<float>()); }
 
+// The photometric compensation a job asks for, then the blend that applies it -- both after the bundle's geometry is final.
+// gain: exposure gains (hip_gain_compensate), one per block of a bx x by grid on every image when bx * by > 1
+// (hip_gain_compensate_blocks); vignetting: grey gains plus the shared falloff curve (hip_vignette_compensate), refused
+// together with block gains.  `gains` and `vignette_poly` receive what the blend used (empty / 0 when it used none).
+struct HipCompensation {
+	bool gain = false;
+	int bx = 1, by = 1;
+	bool vignetting = false;
+};
+template <typename Bundle>
+inline Mat32f hip_compensate_and_blend(const Bundle& b, const HipCompensation& how, std::vector<float>& gains, std::array<float, 3>& vignette_poly) {
+	vignette_poly = {0.f, 0.f, 0.f};
+	if (how.vignetting) {
+		if (how.bx * how.by > 1) { fprintf(stderr, "HipStitcher: vignetting and block gains are exclusive\n"); exit(1); }
+		gains = hip_vignette_compensate(b, vignette_poly);
+		return hip_blend(b, false, gains, vignette_poly);
+	}
+	if (!how.gain) { gains.clear(); return hip_blend(b); }
+	if (how.bx == 1 && how.by == 1) {
+		gains = hip_gain_compensate(b);
+		return hip_blend(b, false, gains);
+	}
+	gains = hip_gain_compensate_blocks(b, how.bx, how.by);
+	return hip_blend(b, false, gains, how.bx, how.by);
+}
+
 // ---- write_rgb(fname, mat) (lib/imgio.cc:25-41,98-113; main.cc:30,226-233): the file is encoded on the device instead of on one
 // host thread.  What both formats share: the bytes of the handle an encoder returned go into fname and the handle is freed
-// (size / copy / release: the format's three C entries), and a host matrix is quantised as write_rgb does it (Color::NO ->
+// (size / copy: the format's C entries; its free is the handle's own), and a host matrix is quantised as write_rgb does it (Color::NO ->
 // white, v * 255 truncated).
-template <typename File>
-inline void hip_write_encoded(const char* fname, File* file, int64_t (*size)(const File*), int (*copy)(op_ctx*, const File*, unsigned char*),
-		void (*release)(File*), const char* who) {
-	std::vector<unsigned char> bytes((size_t)size(file));
-	if (copy(HipContext::get(), file, bytes.data()) != OP_OK) hip_error_exit(who);
-	release(file);
+template <typename File, void (*Free)(File*)>
+inline void hip_write_encoded(const char* fname, HipHandle<File, Free> file, int64_t (*size)(const File*), int (*copy)(op_ctx*, const File*, unsigned char*),
+		const char* who) {
+	std::vector<unsigned char> bytes((size_t)size(file.get()));
+	if (copy(HipContext::get(), file.get(), bytes.data()) != OP_OK) hip_error_exit(who);
+	file.reset();
 	FILE* f = fopen(fname, "wb");
 	if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
 		fprintf(stderr, "%s: cannot write %s\n", who, fname);
@@ -869,36 +954,36 @@ inline std::vector<unsigned char> hip_quantise_rgb(const Mat32f& mat) {
 
 // ---- a .png name: op_canvas_encode_png / op_png_encode_u8 stand in for lodepng.  Same pixels as the reference's file, 8-bit RGB
 // where lodepng is handed RGBA with alpha 255 and reduces it to RGB.
-inline void hip_write_png_file(const char* fname, op_png* png) { hip_write_encoded(fname, png, op_png_size, op_png_copy, op_png_free, "hip_write_png"); }
+inline void hip_write_png_file(const char* fname, HipPng png) { hip_write_encoded(fname, std::move(png), op_png_size, op_png_copy, "hip_write_png"); }
 // the device canvas a blend left behind (op_blend*, op_canvas_crop): the fp32 canvas does not come back at all
 inline void hip_write_png(const char* fname, const op_canvas* canvas) {
-	op_png* png = nullptr;
-	PANO_HIP_CHECK(op_canvas_encode_png(HipContext::get(), canvas, &png));
-	hip_write_png_file(fname, png);
+	HipPng png;
+	PANO_HIP_CHECK(op_canvas_encode_png(HipContext::get(), canvas, hip_out(png)));
+	hip_write_png_file(fname, std::move(png));
 }
 // write_rgb's signature: a matrix in host memory
 inline void hip_write_png(const char* fname, const Mat32f& mat) {
 	const std::vector<unsigned char> rgb = hip_quantise_rgb(mat);
-	op_png* png = nullptr;
-	PANO_HIP_CHECK(op_png_encode_u8(HipContext::get(), rgb.data(), mat.rows(), mat.cols(), &png));
-	hip_write_png_file(fname, png);
+	HipPng png;
+	PANO_HIP_CHECK(op_png_encode_u8(HipContext::get(), rgb.data(), mat.rows(), mat.cols(), hip_out(png)));
+	hip_write_png_file(fname, std::move(png));
 }
 
 // ---- a .jpg name (-> CImg::save_jpeg -> libjpeg): baseline JPEG from op_canvas_encode_jpeg / op_jpeg_encode_u8, every byte what
 // libjpeg writes for the same pixels, quality, sampling and restart interval.  The reference's own file is quality 100 at OP_JPEG_420.
-inline void hip_write_jpeg_file(const char* fname, op_jpeg* jpg) { hip_write_encoded(fname, jpg, op_jpeg_size, op_jpeg_copy, op_jpeg_free, "hip_write_jpeg"); }
+inline void hip_write_jpeg_file(const char* fname, HipJpeg jpg) { hip_write_encoded(fname, std::move(jpg), op_jpeg_size, op_jpeg_copy, "hip_write_jpeg"); }
 // the device canvas a blend left behind (op_blend*, op_canvas_crop)
 inline void hip_write_jpeg(const char* fname, const op_canvas* canvas, int quality = 90, int subsampling = OP_JPEG_420) {
-	op_jpeg* jpg = nullptr;
-	PANO_HIP_CHECK(op_canvas_encode_jpeg(HipContext::get(), canvas, quality, subsampling, &jpg));
-	hip_write_jpeg_file(fname, jpg);
+	HipJpeg jpg;
+	PANO_HIP_CHECK(op_canvas_encode_jpeg(HipContext::get(), canvas, quality, subsampling, hip_out(jpg)));
+	hip_write_jpeg_file(fname, std::move(jpg));
 }
 // write_rgb's signature: a matrix in host memory
 inline void hip_write_jpeg(const char* fname, const Mat32f& pano, int quality = 90, int subsampling = OP_JPEG_420) {
 	const std::vector<unsigned char> rgb = hip_quantise_rgb(pano);
-	op_jpeg* jpg = nullptr;
-	PANO_HIP_CHECK(op_jpeg_encode_u8(HipContext::get(), rgb.data(), pano.rows(), pano.cols(), quality, subsampling, &jpg));
-	hip_write_jpeg_file(fname, jpg);
+	HipJpeg jpg;
+	PANO_HIP_CHECK(op_jpeg_encode_u8(HipContext::get(), rgb.data(), pano.rows(), pano.cols(), quality, subsampling, hip_out(jpg)));
+	hip_write_jpeg_file(fname, std::move(jpg));
 }
 
 #ifndef OPENPANO_WITH_REFERENCE
@@ -974,24 +1059,18 @@ class HipCylinderWarper {
 			const op_config cfg = hip_config_snapshot();
 			Shape2D shape(mat.width(), mat.height());
 			op_image im{mat.ptr(), mat.rows(), mat.cols(), 0, OP_F32};
-			op_canvas* cv = nullptr;
-			PANO_HIP_CHECK(op_cyl_warp(ctx, &cfg, &im, h_factor, &cv));
+			HipCanvas cv;
+			PANO_HIP_CHECK(op_cyl_warp(ctx, &cfg, &im, h_factor, hip_out(cv)));
 			warp(shape, kpts);
-			int h, w;
-			PANO_HIP_CHECK(op_canvas_dims(cv, &h, &w));
-			Mat32f out(h, w, 3);
-			PANO_HIP_CHECK(op_canvas_copy(ctx, cv, out.ptr()));
-			op_canvas_free(cv);
-			mat = out;
+			mat = hip_canvas_to_mat(std::move(cv));
 		}
 		// warp keypoints given image shape
 		void warp(Shape2D& shape, std::vector<Vec2D>& kpts) const {
 			const op_config cfg = hip_config_snapshot();
-			std::vector<double> p(kpts.size() * 2 + 2);
-			for (size_t i = 0; i < kpts.size(); ++i) { p[2 * i] = kpts[i].x; p[2 * i + 1] = kpts[i].y; }
+			std::vector<double> p = hip_flatten(kpts);
 			int nw, nh; double off[2];
 			PANO_HIP_CHECK(op_cyl_warp_shape(&cfg, shape.w, shape.h, h_factor, kpts.empty() ? nullptr : p.data(), (int)kpts.size(), &nw, &nh, off));
-			for (size_t i = 0; i < kpts.size(); ++i) kpts[i] = Vec2D(p[2 * i], p[2 * i + 1]);
+			hip_unflatten(p, kpts);
 			shape.w = nw; shape.h = nh;
 		}
 		// warp image only
@@ -1029,41 +1108,23 @@ inline op_canvas* hip_perspective_correction(const Bundle& b, const op_canvas* c
 // perspective_correction's own signature: a matrix in host memory goes up, the corrected one comes back
 template <typename Bundle>
 inline Mat32f hip_perspective_correction(const Bundle& b, const Mat32f& img) {
-	op_ctx* ctx = HipContext::get();
-	op_canvas* cv = nullptr;
-	PANO_HIP_CHECK(op_canvas_upload(ctx, img.ptr(), img.rows(), img.cols(), &cv));
-	op_canvas* fixed = hip_perspective_correction(b, cv);
-	op_canvas_free(cv);
-	Mat32f out(img.rows(), img.cols(), 3);
-	PANO_HIP_CHECK(op_canvas_copy(ctx, fixed, out.ptr()));
-	op_canvas_free(fixed);
-	return out;
+	HipCanvas cv;
+	PANO_HIP_CHECK(op_canvas_upload(HipContext::get(), img.ptr(), img.rows(), img.cols(), hip_out(cv)));
+	HipCanvas fixed(hip_perspective_correction(b, cv.get()));
+	cv.reset();
+	return hip_canvas_to_mat(std::move(fixed));
 }
 
 #ifndef OPENPANO_WITH_REFERENCE
-// ===================================== STITCHER =====================================
-// Stitcher (stitch/stitcher.hh:17-62, stitcher.cc:32-198) + StitcherBase (stitcherbase.hh:17-64),
-// standalone: the whole of Stitcher::build() with the device stages batched -- one SIFT call for
-// all images, one match call and one RANSAC call for the whole pair list -- and the host stages
-// (camera estimation / bundle adjustment, pano_camera.hh) in between.  Members keep the
-// reference's names; `cameras` and `base_seed` (RANSAC seed injection) are additions.
+// ===================================== STITCHER BASE =====================================
 // ImageRef(fname) for a list of baseline JPEG files (stitch/imageref.hh:15-31): only the headers are read (op_jpeg_probe), for the
-// shapes; with apply_exif_orientation a file of orientation 5..8 enters as w x h.  Shared by the two stitchers' file constructors.
+// shapes; with apply_exif_orientation a file of orientation 5..8 enters as w x h.  For HipStitcherBase's file constructor.
 inline void hip_jpeg_image_refs(const std::vector<std::string>& paths, bool apply_exif_orientation, std::vector<ImageRef>& imgs) {
 	for (auto& p : paths) {
-		FILE* f = fopen(p.c_str(), "rb");
-		if (!f) { fprintf(stderr, "File \"%s\" not exists!\n", p.c_str()); exit(1); }
-		std::vector<unsigned char> head(1 << 20);      // SOF0 comes before the scan; a megabyte holds any EXIF before it
-		const size_t got = fread(head.data(), 1, head.size(), f);
-		bool whole = got < head.size();
-		if (!whole) {
-			fseek(f, 0, SEEK_END); const long all = ftell(f); fseek(f, 0, SEEK_SET);
-			head.resize((size_t)all);
-			whole = fread(head.data(), 1, head.size(), f) == head.size();
-		} else head.resize(got);
-		fclose(f);
+		std::vector<unsigned char> head = hip_read_file(p, 1 << 20);     // SOF0 comes before the scan; a megabyte holds any EXIF before it
+		if (head.size() == (size_t)1 << 20) head = hip_read_file(p);     // a longer file is read whole
 		int h = 0, w = 0, sampling = 0;
-		if (!whole || op_jpeg_probe(head.data(), (int64_t)head.size(), &h, &w, &sampling) != OP_OK) hip_error_exit(p);
+		if (op_jpeg_probe(head.data(), (int64_t)head.size(), &h, &w, &sampling) != OP_OK) hip_error_exit(p);
 		if (apply_exif_orientation) {
 			int o = 1;
 			if (op_jpeg_exif(head.data(), (int64_t)head.size(), &o, nullptr) != OP_OK) hip_error_exit(p);
@@ -1074,30 +1135,83 @@ inline void hip_jpeg_image_refs(const std::vector<std::string>& paths, bool appl
 	}
 }
 
-class HipStitcher {
+// What the two stitchers share (the part StitcherBase has in the reference): the image list from matrices or from camera files,
+// the features and keypoints of all images from one batched call, and the bundle whose components point at the images.
+class HipStitcherBase {
 	public:
-		explicit HipStitcher(const std::vector<Mat32f>& mats, uint32_t base_seed = 42u): base_seed(base_seed) {
-			if (mats.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", mats.size()); exit(1); }   // stitcherbase.hh:46-48
+		HipStitcherBase(const HipStitcherBase&) = delete;
+		HipStitcherBase& operator=(const HipStitcherBase&) = delete;
+
+		std::vector<ImageRef> imgs;
+		HipFeatureSet feats;                                        // StitcherBase::feats + the resident device copy
+		std::vector<std::vector<Vec2D>> keypoints;
+		ConnectedImages bundle;
+		uint32_t base_seed;
+		// resident views: calc_feature uploads the images once (bytes when they are exact k / 255, fp32 otherwise) and every
+		// later stage reads that upload -- SIFT, and then the overlap passes and the blend (HipStitcher) or the cylinder
+		// pre-warp (HipCylinderStitcher); off by default.  The panorama is the same bit for bit.
+		bool resident_views = false;
+		// with jpeg_paths: calc_feature() decodes every view turned upright by its file's EXIF orientation
+		// (hip_read_jpeg_views(.., true)); off by default, as the reference ignores the tag.  Set through the constructor,
+		// which takes the shapes of the views
+		bool apply_exif_orientation = false;
+		// set by the constructor that takes files: the views are decoded on the device and always resident
+		std::vector<std::string> jpeg_paths;
+
+		std::vector<Shape2D> shapes() const {
+			std::vector<Shape2D> s;
+			for (auto& r : imgs) s.push_back(r.shape());
+			return s;
+		}
+		void calc_feature() {                                       // stitcherbase.cc:9-27
+			std::vector<const Mat32f*> ptrs;
+			for (auto& r : imgs) ptrs.push_back(r.img);
+			bundle.views = nullptr;                                 // the previous upload is released by the assignment below
+			if (!jpeg_paths.empty()) feats = HipSIFTDetector().calc_feature(hip_read_jpeg_views(HipContext::get(), jpeg_paths, apply_exif_orientation));
+			else feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
+			keypoints.clear();
+			for (auto& f : feats.feats) keypoints.push_back(hip_keypoints(f));
+		}
+		void free_feature() { feats = HipFeatureSet(); keypoints.clear(); }     // stitcherbase.cc:29-33; the views go with it
+
+	protected:
+		HipStitcherBase(const std::vector<Mat32f>& mats, uint32_t base_seed, bool resident_views): HipStitcherBase(mats.size(), base_seed) {
+			this->resident_views = resident_views;
 			for (auto& m : mats) imgs.emplace_back(m);
 			for (auto& r : imgs) bundle.component.emplace_back(&r);
 		}
 		// From camera files: jpeg_paths stands in place of the Mat32f images (ImageRef(fname), stitch/imageref.hh:15-31).  Only
 		// the headers are read here (op_jpeg_probe, for the shapes); calc_feature() decodes the files on the device
-		// (hip_read_jpeg_views) and SIFT, the overlap passes and the blend read those views: build() touches no host pixel.
+		// (hip_read_jpeg_views) and every later stage reads those views: a build touches no host pixel.
 		// apply_exif_orientation: the views are turned upright by their files' EXIF orientation, so a file of orientation
 		// 5..8 enters the job as w x h.
-		explicit HipStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u, bool apply_exif_orientation = false):
-				base_seed(base_seed), apply_exif_orientation(apply_exif_orientation), jpeg_paths(paths) {
-			if (paths.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", paths.size()); exit(1); }   // stitcherbase.hh:46-48
+		HipStitcherBase(const std::vector<std::string>& paths, uint32_t base_seed, bool apply_exif_orientation): HipStitcherBase(paths.size(), base_seed) {
+			this->apply_exif_orientation = apply_exif_orientation;
+			jpeg_paths = paths;
 			hip_jpeg_image_refs(paths, apply_exif_orientation, imgs);
 			for (auto& r : imgs) bundle.component.emplace_back(&r);
 		}
-		HipStitcher(const HipStitcher&) = delete;
-		HipStitcher& operator=(const HipStitcher&) = delete;
+		~HipStitcherBase() = default;
+	private:
+		HipStitcherBase(size_t n, uint32_t base_seed): base_seed(base_seed) {
+			if (n <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", n); exit(1); }   // stitcherbase.hh:46-48
+		}
+};
+
+// ===================================== STITCHER =====================================
+// Stitcher (stitch/stitcher.hh:17-62, stitcher.cc:32-198), standalone: the whole of Stitcher::build() with the device stages
+// batched -- one SIFT call for all images, one match call and one RANSAC call for the whole pair list -- and the host stages
+// (camera estimation / bundle adjustment, pano_camera.hh) in between.  Members keep the reference's names; `cameras` and
+// `base_seed` (RANSAC seed injection) are additions.
+class HipStitcher : public HipStitcherBase {
+	public:
+		explicit HipStitcher(const std::vector<Mat32f>& mats, uint32_t base_seed = 42u): HipStitcherBase(mats, base_seed, false) {}
+		explicit HipStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u, bool apply_exif_orientation = false):
+				HipStitcherBase(paths, base_seed, apply_exif_orientation) {}
 
 		Mat32f build() {                                            // stitcher.cc:32-64
 			calc_feature();
-			bundle.views = resident_views || !jpeg_paths.empty() ? feats.views : nullptr;
+			bundle.views = resident_views || !jpeg_paths.empty() ? feats.views.get() : nullptr;
 			pairwise_matches.assign(imgs.size(), std::vector<MatchInfo>(imgs.size()));
 			if (config::ORDERED_INPUT) linear_pairwise_match();
 			else pairwise_match();
@@ -1106,28 +1220,12 @@ class HipStitcher {
 			else build_linear_simple();
 			bundle.proj_method = config::ESTIMATE_CAMERA ? ConnectedImages::spherical : ConnectedImages::flat;
 			bundle.update_proj_range();
-			vignette_poly = {0.f, 0.f, 0.f};
-			if (vignetting) {
-				if (gain_blocks_x * gain_blocks_y > 1) { fprintf(stderr, "HipStitcher: vignetting and block gains are exclusive\n"); exit(1); }
-				gains = hip_vignette_compensate(bundle, vignette_poly);   // after the homographies are final
-				return hip_blend(bundle, false, gains, vignette_poly);
-			}
-			if (!gain_compensation) { gains.clear(); return bundle.blend(); }
-			if (gain_blocks_x == 1 && gain_blocks_y == 1) {
-				gains = hip_gain_compensate(bundle);                // after the homographies are final
-				return hip_blend(bundle, false, gains);
-			}
-			gains = hip_gain_compensate_blocks(bundle, gain_blocks_x, gain_blocks_y);
-			return hip_blend(bundle, false, gains, gain_blocks_x, gain_blocks_y);
+			const HipCompensation how{gain_compensation, gain_blocks_x, gain_blocks_y, vignetting};
+			return hip_compensate_and_blend(bundle, how, gains, vignette_poly);   // after the homographies are final
 		}
 
-		std::vector<ImageRef> imgs;
-		HipFeatureSet feats;                                        // StitcherBase::feats + the resident device copy
-		std::vector<std::vector<Vec2D>> keypoints;
 		std::vector<std::vector<MatchInfo>> pairwise_matches;
-		ConnectedImages bundle;
 		std::vector<Camera> cameras;
-		uint32_t base_seed;
 		// exposure (gain) compensation before the blend (hip_gain_compensate): an extension, off by default; `gains` holds
 		// the n x 3 gains the last build() used (empty when it used none).  gain_blocks_x / _y > 1: one gain per block of
 		// that grid on every image (hip_gain_compensate_blocks); `gains` then holds n * by * bx * 3
@@ -1138,44 +1236,12 @@ class HipStitcher {
 		bool vignetting = false;
 		std::array<float, 3> vignette_poly = {0.f, 0.f, 0.f};
 		std::vector<float> gains;
-		// resident views: calc_feature uploads the images once (bytes when they are exact k / 255, fp32 otherwise) and SIFT,
-		// the overlap passes and the blend all read that upload; off by default.  The panorama is the same bit for bit.
-		bool resident_views = false;
-		// with jpeg_paths: calc_feature() decodes every view turned upright by its file's EXIF orientation
-		// (hip_read_jpeg_views(.., true)); off by default, as the reference ignores the tag.  Set through the constructor,
-		// which takes the shapes of the views
-		bool apply_exif_orientation = false;
-		// set by the constructor that takes files: the views are decoded on the device and always resident
-		std::vector<std::string> jpeg_paths;
 
-		void calc_feature() {                                       // stitcherbase.cc:9-27
-			std::vector<const Mat32f*> ptrs;
-			for (auto& r : imgs) ptrs.push_back(r.img);
-			bundle.views = nullptr;                                 // the previous upload is released by the assignment below
-			if (!jpeg_paths.empty()) feats = HipSIFTDetector().calc_feature(hip_read_jpeg_views(HipContext::get(), jpeg_paths, apply_exif_orientation));
-			else feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
-			keypoints.resize(imgs.size());
-			for (size_t k = 0; k < imgs.size(); ++k) {
-				keypoints[k].clear();
-				for (auto& d : feats.feats[k]) keypoints[k].emplace_back(d.coor);
-			}
-		}
-		void pairwise_match() {                                     // stitcher.cc:96-113
-			std::vector<std::pair<int, int>> tasks;
-			for (int i = 0; i < (int)imgs.size(); ++i) for (int j = i + 1; j < (int)imgs.size(); ++j) tasks.emplace_back(i, j);
-			match_tasks(tasks, false);
-		}
-		void linear_pairwise_match() {                              // stitcher.cc:115-136
-			const int n = (int)imgs.size();
-			std::vector<std::pair<int, int>> tasks;
-			for (int i = 0; i < n; ++i) tasks.emplace_back(i, (i + 1) % n);
-			match_tasks(tasks, true);
-		}
+		void pairwise_match() { match_tasks(hip_default_tasks((int)imgs.size(), false), false); }          // stitcher.cc:96-113
+		void linear_pairwise_match() { match_tasks(hip_default_tasks((int)imgs.size(), true), true); }      // stitcher.cc:115-136
 		void assign_center() { bundle.identity_idx = (int)imgs.size() >> 1; }   // stitcher.cc:138-141
 		void estimate_camera() {                                    // stitcher.cc:143-158
-			std::vector<Shape2D> shapes;
-			for (auto& m : imgs) shapes.emplace_back(m.shape());
-			cameras = CameraEstimator{pairwise_matches, shapes}.estimate();
+			cameras = CameraEstimator{pairwise_matches, shapes()}.estimate();
 			for (size_t i = 0; i < imgs.size(); ++i) {
 				bundle.component[i].homo_inv = cameras[i].K() * cameras[i].R;
 				bundle.component[i].homo = cameras[i].Rinv() * cameras[i].K().inverse();
@@ -1206,9 +1272,7 @@ class HipStitcher {
 		// match_image (stitcher.cc:66-94) for a whole task list: one match call + one RANSAC call,
 		// then the reference's bookkeeping per connected pair
 		void match_tasks(const std::vector<std::pair<int, int>>& tasks, bool linear) {
-			std::vector<Shape2D> shapes;
-			for (auto& r : imgs) shapes.push_back(r.shape());
-			record_matches(tasks, hip_match_images(feats, shapes, tasks, base_seed), linear);
+			record_matches(tasks, hip_match_images(feats, shapes(), tasks, base_seed), linear);
 		}
 		void record_matches(const std::vector<std::pair<int, int>>& tasks, const std::vector<std::pair<bool, MatchInfo>>& infos, bool linear) {
 			const int n = (int)imgs.size();
@@ -1242,23 +1306,13 @@ class HipStitcher {
 // op_ransac_pairs per update_h_factor attempt over all right-hand pairs, one for all left-hand pairs, each over coordinates-only
 // features (the warped keypoints).  Every estimate of one build() is seeded with base_seed (the reference seeds each from
 // std::random_device).  Members keep the reference's names; `attempts`, `best_factor`, `corners`, `inv` record what a build did.
-class HipCylinderStitcher {
+class HipCylinderStitcher : public HipStitcherBase {
 	public:
 		explicit HipCylinderStitcher(const std::vector<Mat32f>& mats, uint32_t base_seed = 42u, bool resident_views = false):
-				base_seed(base_seed), resident_views(resident_views) {
-			if (mats.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", mats.size()); exit(1); }   // stitcherbase.hh:46-48
-			for (auto& m : mats) imgs.emplace_back(m);
-			for (auto& r : imgs) bundle.component.emplace_back(&r);
-		}
+				HipStitcherBase(mats, base_seed, resident_views) {}
 		// From camera files, as HipStitcher(paths): the views are decoded on the device and are always resident
 		explicit HipCylinderStitcher(const std::vector<std::string>& paths, uint32_t base_seed = 42u, bool apply_exif_orientation = false):
-				base_seed(base_seed), apply_exif_orientation(apply_exif_orientation), jpeg_paths(paths) {
-			if (paths.size() <= 1) { fprintf(stderr, "Cannot stitch with only %zu images.\n", paths.size()); exit(1); }   // stitcherbase.hh:46-48
-			hip_jpeg_image_refs(paths, apply_exif_orientation, imgs);
-			for (auto& r : imgs) bundle.component.emplace_back(&r);
-		}
-		HipCylinderStitcher(const HipCylinderStitcher&) = delete;
-		HipCylinderStitcher& operator=(const HipCylinderStitcher&) = delete;
+				HipStitcherBase(paths, base_seed, apply_exif_orientation) {}
 		~HipCylinderStitcher() { free_warped(); }
 
 		// CylinderStitcher::build() (cylstitcher.cc:20-29) with the panorama left on the device; the caller owns it (op_canvas_free).
@@ -1270,37 +1324,14 @@ class HipCylinderStitcher {
 			free_feature();
 			bundle.proj_method = ConnectedImages::flat;
 			bundle.update_proj_range();
-			op_canvas* ret = blend();
-			op_canvas* fixed = perspective_correction(ret);
-			op_canvas_free(ret);
-			if (crop) {
-				op_canvas* cc = nullptr;
-				PANO_HIP_CHECK(op_canvas_crop(HipContext::get(), fixed, &cc, nullptr, nullptr));
-				op_canvas_free(fixed);
-				fixed = cc;
-			}
-			return fixed;
+			HipCanvas ret(blend());
+			HipCanvas fixed(perspective_correction(ret.get()));
+			ret.reset();
+			if (crop) hip_crop_in_place(fixed);
+			return fixed.release();
 		}
-		Mat32f build() {
-			op_canvas* cv = build_canvas();
-			int h, w;
-			PANO_HIP_CHECK(op_canvas_dims(cv, &h, &w));
-			Mat32f out(h, w, 3);
-			PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), cv, out.ptr()));
-			op_canvas_free(cv);
-			return out;
-		}
+		Mat32f build() { return hip_canvas_to_mat(HipCanvas(build_canvas())); }
 
-		std::vector<ImageRef> imgs;
-		HipFeatureSet feats;                                        // StitcherBase::feats + the resident device copy
-		std::vector<std::vector<Vec2D>> keypoints;
-		ConnectedImages bundle;
-		uint32_t base_seed;
-		// resident views (the Mat constructor): calc_feature uploads the images once and SIFT and the pre-warp read that upload;
-		// off by default.  The panorama is the same bit for bit.
-		bool resident_views = false;
-		bool apply_exif_orientation = false;
-		std::vector<std::string> jpeg_paths;
 		// what the last build did: every update_h_factor attempt, the factor the pre-warp used, the four corners and the map of
 		// the perspective correction
 		struct Attempt { float factor, slope; bool ok; };
@@ -1309,19 +1340,6 @@ class HipCylinderStitcher {
 		double corners[8] = {0}, inv[9] = {0};
 		// the pre-warped views, on the device (what imgs[k].img becomes in the reference, cylstitcher.cc:66-67)
 		std::vector<op_canvas*> warped;
-
-		void calc_feature() {                                       // stitcherbase.cc:9-27
-			std::vector<const Mat32f*> ptrs;
-			for (auto& r : imgs) ptrs.push_back(r.img);
-			if (!jpeg_paths.empty()) feats = HipSIFTDetector().calc_feature(hip_read_jpeg_views(HipContext::get(), jpeg_paths, apply_exif_orientation));
-			else feats = HipSIFTDetector().calc_feature(ptrs, resident_views);
-			keypoints.resize(imgs.size());
-			for (size_t k = 0; k < imgs.size(); ++k) {
-				keypoints[k].clear();
-				for (auto& d : feats.feats[k]) keypoints[k].emplace_back(d.coor);
-			}
-		}
-		void free_feature() { feats = HipFeatureSet(); keypoints.clear(); }     // stitcherbase.cc:29-33; the views go with it
 
 		void build_warp() {                                         // cylstitcher.cc:31-87
 			op_ctx* ctx = HipContext::get();
@@ -1334,18 +1352,17 @@ class HipCylinderStitcher {
 			// the two handles the RANSAC calls read
 			std::vector<int> pr;
 			for (int k = 0; k + 1 < n; ++k) { pr.push_back(k); pr.push_back(k + 1); }
-			op_matches* all = nullptr;
-			PANO_HIP_CHECK(op_match_pairs(ctx, &cfg, feats.handle, pr.data(), n - 1, &all));
+			HipMatches all;
+			PANO_HIP_CHECK(op_match_pairs(ctx, &cfg, feats.handle.get(), pr.data(), n - 1, hip_out(all)));
 			std::vector<int64_t> off((size_t)n);
-			std::vector<int> idx((size_t)op_matches_total(all) * 2 + 2);
-			PANO_HIP_CHECK(op_matches_copy_all(all, idx.data(), off.data()));
-			op_matches_free(all);
+			std::vector<int> idx((size_t)op_matches_total(all.get()) * 2 + 2);
+			PANO_HIP_CHECK(op_matches_copy_all(all.get(), idx.data(), off.data()));
+			all.reset();
 			for (int k = 0; k < mid; ++k) for (int64_t q = off[k]; q < off[k + 1]; ++q) std::swap(idx[2 * q], idx[2 * q + 1]);
 			std::vector<const int*> lists; std::vector<int> counts;
 			for (int k = 0; k + 1 < n; ++k) { lists.push_back(idx.data() + 2 * off[k]); counts.push_back((int)(off[k + 1] - off[k])); }
-			right_matches = left_matches = nullptr;
-			if (n - 1 - mid > 0) PANO_HIP_CHECK(op_matches_from_host(lists.data() + mid, counts.data() + mid, n - 1 - mid, &right_matches));
-			if (mid > 0) PANO_HIP_CHECK(op_matches_from_host(lists.data(), counts.data(), mid, &left_matches));
+			if (n - 1 - mid > 0) PANO_HIP_CHECK(op_matches_from_host(lists.data() + mid, counts.data() + mid, n - 1 - mid, hip_out(right_matches)));
+			if (mid > 0) PANO_HIP_CHECK(op_matches_from_host(lists.data(), counts.data(), mid, hip_out(left_matches)));
 
 			std::vector<Homography> bestmat;
 			float minslope = std::numeric_limits<float>::max();
@@ -1370,7 +1387,7 @@ class HipCylinderStitcher {
 			warped.assign((size_t)n, nullptr);
 			for (int k = 0; k < n; ++k) {
 				op_image im{imgs[k].img ? imgs[k].img->ptr() : nullptr, imgs[k].height(), imgs[k].width(), 0, OP_F32};
-				if (feats.views) PANO_HIP_CHECK(op_views_image(feats.views, k, &im));
+				if (feats.views) PANO_HIP_CHECK(op_views_image(feats.views.get(), k, &im));
 				PANO_HIP_CHECK(op_cyl_warp(ctx, &cfg, &im, (double)bestfactor, &warped[k]));
 				Shape2D shape = imgs[k].shape();
 				warper.warp(shape, keypoints[k]);
@@ -1383,15 +1400,14 @@ class HipCylinderStitcher {
 				for (int i = 0; i < mid; ++i) { pairs.push_back(i + 1); pairs.push_back(i); }
 				for (int i = 0; i <= mid; ++i) { shapes.push_back(imgs[i].width()); shapes.push_back(imgs[i].height()); }
 				std::vector<Homography> homo;
-				const int failed = estimate(left_matches, keypoints.data(), mid + 1, pairs, shapes, homo);
+				const int failed = estimate(left_matches.get(), keypoints.data(), mid + 1, pairs, shapes, homo);
 				// Can match before, but not here. This would be a bug.
 				if (failed >= 0) { fprintf(stderr, "error: Failed to match between image %d and %d.\n", failed, failed + 1); exit(1); }
 				for (int i = 0; i < mid; ++i) bundle.component[i].homo = homo[i];
 			}
 			for (int i = mid - 2; i >= 0; --i) bundle.component[i].homo = bundle.component[i + 1].homo * bundle.component[i].homo;
 			bundle.calc_inverse_homo();
-			op_matches_free(right_matches); op_matches_free(left_matches);
-			right_matches = left_matches = nullptr;
+			right_matches.reset(); left_matches.reset();
 		}
 
 		// cylstitcher.cc:89-137
@@ -1409,7 +1425,7 @@ class HipCylinderStitcher {
 			std::vector<int> pairs;                                 // in nowimgs' numbering: only views start .. n - 1 go up
 			for (int k = 1; k < len; ++k) { pairs.push_back(k - 1); pairs.push_back(k); }
 			std::vector<Homography> nowmat;                         // size = len - 1
-			const bool failed = estimate(right_matches, nowkpts.data(), len, pairs, shapes, nowmat) >= 0;
+			const bool failed = estimate(right_matches.get(), nowkpts.data(), len, pairs, shapes, nowmat) >= 0;
 			if (failed) { attempts.push_back(Attempt{nowfactor, 0.f, false}); return 0; }
 			for (int k = 1; k < len - 1; ++k) nowmat[k] = nowmat[k - 1] * nowmat[k];    // transform to nowimgs[0] == imgs[mid]
 			// check the slope of the result image
@@ -1431,20 +1447,15 @@ class HipCylinderStitcher {
 			op_ctx* ctx = HipContext::get();
 			const op_config cfg = hip_config_snapshot();
 			const int n = (int)imgs.size();
-			const Vec2D res = bundle.get_final_resolution();
 			op_blend_geom g;
-			g.proj_method = (int)bundle.proj_method;
-			g.proj_min[0] = bundle.proj_range.min.x; g.proj_min[1] = bundle.proj_range.min.y;
-			g.proj_max[0] = bundle.proj_range.max.x; g.proj_max[1] = bundle.proj_range.max.y;
-			g.resolution[0] = res.x; g.resolution[1] = res.y;
+			hip_bundle_geom(bundle, g);
 			std::vector<op_blend_image> ims((size_t)n);
 			for (int i = 0; i < n; ++i) {
 				auto& c = bundle.component[i];
 				ims[i].data = op_canvas_device(warped[i]); ims[i].on_device = OP_SRC_DEVICE;
 				ims[i].h = c.imgptr->height(); ims[i].w = c.imgptr->width();
 				PANO_HIP_CHECK(op_canvas_dims(warped[i], &ims[i].mat_h, &ims[i].mat_w));
-				for (int k = 0; k < 9; ++k) ims[i].homo_inv[k] = c.homo_inv[k];
-				ims[i].range[0] = c.range.min.x; ims[i].range[1] = c.range.min.y; ims[i].range[2] = c.range.max.x; ims[i].range[3] = c.range.max.y;
+				hip_component_geom(c, ims[i]);
 			}
 			op_canvas* cv = nullptr;
 			PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, &cv));
@@ -1455,7 +1466,7 @@ class HipCylinderStitcher {
 		op_canvas* perspective_correction(const op_canvas* img) { return hip_perspective_correction(bundle, img, corners, inv); }
 
 	private:
-		op_matches *right_matches = nullptr, *left_matches = nullptr;   // alive inside build_warp only
+		HipMatches right_matches, left_matches;                         // alive inside build_warp only
 		void free_warped() { for (op_canvas* c : warped) op_canvas_free(c); warped.clear(); }
 		// One op_ransac_pairs over coordinates-only features (INTEGRATION hook 3) of the n views the pairs read: kpts and (w, h)
 		// per view, the pair list that goes with `m`, all three in the numbering of those n views.  homo[p] = the estimate of
@@ -1465,26 +1476,18 @@ class HipCylinderStitcher {
 			op_ctx* ctx = HipContext::get();
 			const op_config cfg = hip_config_snapshot();
 			const int np = (int)pairs.size() / 2;
-			std::vector<std::vector<double>> flat((size_t)n);
-			std::vector<const double*> cp((size_t)n); std::vector<int> counts((size_t)n);
-			for (int k = 0; k < n; ++k) {
-				counts[k] = (int)kpts[k].size();
-				flat[k].resize((size_t)counts[k] * 2 + 2);
-				for (int i = 0; i < counts[k]; ++i) { flat[k][2 * i] = kpts[k][i].x; flat[k][2 * i + 1] = kpts[k][i].y; }
-				cp[k] = flat[k].data();
-			}
-			op_features* f = nullptr;
-			PANO_HIP_CHECK(op_features_from_host(ctx, nullptr, cp.data(), counts.data(), n, &f));
+			std::vector<const std::vector<Vec2D>*> lists;
+			for (int k = 0; k < n; ++k) lists.push_back(&kpts[k]);
+			const HipFeatures f = hip_features_from_keypoints(ctx, lists);
 			const std::vector<uint32_t> seeds((size_t)np, base_seed);
-			op_ransac_result* r = nullptr;
-			PANO_HIP_CHECK(op_ransac_pairs(ctx, &cfg, f, m, pairs.data(), np, shapes.data(), seeds.data(), 0, &r));
+			HipRansac r;
+			PANO_HIP_CHECK(op_ransac_pairs(ctx, &cfg, f.get(), m, pairs.data(), np, shapes.data(), seeds.data(), 0, hip_out(r)));
 			homo.assign((size_t)np, Homography::I());
 			int failed = -1;
 			for (int p = 0; p < np; ++p) {
-				if (!op_ransac_ok(r, p)) { if (failed < 0) failed = pairs[2 * p + 1]; continue; }
-				PANO_HIP_CHECK(op_ransac_homo(r, p, homo[p].data));
+				if (!op_ransac_ok(r.get(), p)) { if (failed < 0) failed = pairs[2 * p + 1]; continue; }
+				PANO_HIP_CHECK(op_ransac_homo(r.get(), p, homo[p].data));
 			}
-			op_ransac_free(r); op_features_free(f);
 			return failed;
 		}
 };

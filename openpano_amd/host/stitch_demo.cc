@@ -63,23 +63,41 @@
 
 using namespace pano;
 
-// --jpeg PATH, --jpeg-quality Q, --jpeg-444
-static const char* g_jpeg_path = nullptr;
-static int g_jpeg_quality = 90;
-static bool g_jpeg_444 = false;
+// what the command line asks for
+struct Options {
+	const char* out_path = nullptr;
+	uint32_t base_seed = 42u;
+	std::string mode;
+	HipCompensation compensation;       // --gain-compensation, --gain-blocks BXxBY, --vignetting
+	const char* png_path = nullptr;     // --png PATH
+	const char* jpeg_path = nullptr;    // --jpeg PATH, --jpeg-quality Q, --jpeg-444
+	int jpeg_quality = 90;
+	bool jpeg_444 = false;
+	bool resident = false;              // --resident-views
+	const char* jpeg_list = nullptr;    // --jpeg-list PATH, --jpeg-orient
+	bool jpeg_orient = false;
+	bool crop = false, profile = false; // --crop, --profile
+};
 
 template <typename T> static void put(FILE* f, const T* p, size_t n) { if (n && fwrite(p, sizeof(T), n, f) != n) { perror("write"); exit(1); } }
 template <typename T> static void put1(FILE* f, T v) { put(f, &v, 1); }
-
-// 3x3 product (Homography::operator*, stitch/homography.cc:41-48)
-static Homography mul(const Homography& a, const Homography& b) {
-	Homography r;
-	for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
-		double s = 0;
-		for (int k = 0; k < 3; ++k) s += a[i * 3 + k] * b[k * 3 + j];
-		r[i * 3 + j] = s;
-	}
-	return r;
+// int32 H, W ; H*W*3 f32, from host memory or from a device canvas
+static void put_mat(FILE* fo, const Mat32f& m) {
+	put1<int32_t>(fo, m.rows()); put1<int32_t>(fo, m.cols());
+	put(fo, m.ptr(), (size_t)m.rows() * m.cols() * 3);
+}
+static void put_canvas(FILE* fo, const op_canvas* cv) {
+	int h, w;
+	PANO_HIP_CHECK(op_canvas_dims(cv, &h, &w));
+	std::vector<float> px((size_t)h * w * 3);
+	if (!px.empty()) PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), cv, px.data()));
+	put1<int32_t>(fo, h); put1<int32_t>(fo, w);
+	put(fo, px.data(), px.size());
+}
+// the files of --png / --jpeg, encoded on the device from a host matrix or from a device canvas
+template <typename Pano> static void write_files(const Options& o, const Pano& pano) {
+	if (o.png_path) hip_write_png(o.png_path, pano);
+	if (o.jpeg_path) hip_write_jpeg(o.jpeg_path, pano, o.jpeg_quality, o.jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
 }
 
 static void put_features(FILE* fo, const HipFeatureSet& fs) {
@@ -90,10 +108,9 @@ static void put_features(FILE* fo, const HipFeatureSet& fs) {
 		fprintf(stderr, "Image %zu has %zu features\n", k, fs.feats[k].size());
 	}
 }
-static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::pair<int, int>>& tasks,
+// pwmatcher: has matched `tasks` already (precompute)
+static void put_pairs(FILE* fo, const PairWiseMatcher& pwmatcher, const std::vector<std::pair<int, int>>& tasks,
 		const std::vector<std::pair<bool, MatchInfo>>& infos) {
-	PairWiseMatcher pwmatcher(fs);
-	pwmatcher.precompute(tasks);
 	put1<int32_t>(fo, (int32_t)tasks.size());
 	for (size_t p = 0; p < tasks.size(); ++p) {
 		MatchData md = pwmatcher.match(tasks[p].first, tasks[p].second);
@@ -112,23 +129,22 @@ static void put_pairs(FILE* fo, const HipFeatureSet& fs, const std::vector<std::
 
 // Stitcher::build() under ESTIMATE_CAMERA (stitch/stitcher.cc:32-64), stage by stage so that every
 // intermediate can be written out
-static int run_camera_mode(Stitcher& st, const char* out_path, uint32_t base_seed, bool ordered, bool gain, int gbx, int gby,
-		bool vig, const char* png_path, bool resident) {
-	st.resident_views = resident;
-	FILE* fo = fopen(out_path, "wb");
-	if (!fo) { perror(out_path); return 2; }
+static int run_camera_mode(Stitcher& st, const Options& o) {
+	const bool ordered = o.mode == "camera_ordered";
+	const HipCompensation& how = o.compensation;
+	st.resident_views = o.resident;
+	FILE* fo = fopen(o.out_path, "wb");
+	if (!fo) { perror(o.out_path); return 2; }
 	st.calc_feature();
-	st.bundle.views = resident ? st.feats.views : nullptr;     // what HipStitcher::build() does under resident_views
+	st.bundle.views = o.resident ? st.feats.views.get() : nullptr;     // the overlap passes and the blend read the upload
 	put_features(fo, st.feats);
 	const int n = (int)st.imgs.size();
 	st.pairwise_matches.assign(n, std::vector<MatchInfo>(n));
-	std::vector<std::pair<int, int>> tasks;
-	if (ordered) for (int i = 0; i < n; ++i) tasks.emplace_back(i, (i + 1) % n);
-	else for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) tasks.emplace_back(i, j);
-	std::vector<Shape2D> shapes;
-	for (auto& r : st.imgs) shapes.push_back(r.shape());
-	auto infos = hip_match_images(st.feats, shapes, tasks, base_seed);
-	put_pairs(fo, st.feats, tasks, infos);
+	const std::vector<std::pair<int, int>> tasks = hip_default_tasks(n, ordered);
+	auto infos = hip_match_images(st.feats, st.shapes(), tasks, o.base_seed);
+	PairWiseMatcher pwmatcher(st.feats);
+	pwmatcher.precompute(tasks);
+	put_pairs(fo, pwmatcher, tasks, infos);
 	st.record_matches(tasks, infos, ordered);
 	st.assign_center();
 	st.estimate_camera();
@@ -140,23 +156,16 @@ static int run_camera_mode(Stitcher& st, const char* out_path, uint32_t base_see
 	}
 	st.bundle.proj_method = ConnectedImages::spherical;
 	st.bundle.update_proj_range();
-	const bool blocks = gain && gbx * gby > 1;
-	if (vig) st.gains = hip_vignette_compensate(st.bundle, st.vignette_poly);   // what HipStitcher::build() does under vignetting
-	else if (blocks) st.gains = hip_gain_compensate_blocks(st.bundle, gbx, gby);   // what HipStitcher::build() does under gain_blocks_x / _y
-	else if (gain) st.gains = hip_gain_compensate(st.bundle);     // what HipStitcher::build() does under gain_compensation
-	Mat32f pano = vig ? hip_blend(st.bundle, false, st.gains, st.vignette_poly) : blocks ? hip_blend(st.bundle, false, st.gains, gbx, gby)
-	            : gain ? hip_blend(st.bundle, false, st.gains) : st.bundle.blend();
-	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
-	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
+	Mat32f pano = hip_compensate_and_blend(st.bundle, how, st.gains, st.vignette_poly);
+	put_mat(fo, pano);
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
-	if (png_path) hip_write_png(png_path, pano);
-	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
-	if (gain || vig) {
+	write_files(o, pano);
+	if (how.gain || how.vignetting) {
 		put(fo, st.gains.data(), st.gains.size());
 		const size_t per = st.gains.size() / n;      // 3 per image, or 3 per block
 		for (int k = 0; k < n; ++k) fprintf(stderr, "gain %d: %g %g %g\n", k, st.gains[per * k], st.gains[per * k + 1], st.gains[per * k + 2]);
 	}
-	if (vig) {
+	if (how.vignetting) {
 		put(fo, st.vignette_poly.data(), 3);
 		fprintf(stderr, "vignetting curve: a = %g %g %g\n", st.vignette_poly[0], st.vignette_poly[1], st.vignette_poly[2]);
 	}
@@ -165,39 +174,28 @@ static int run_camera_mode(Stitcher& st, const char* out_path, uint32_t base_see
 }
 
 // Stitcher::build() as a client calls it, gain compensation per HipStitcher::gain_compensation
-static int run_build(Stitcher& st, const char* out_path, bool gain, int gbx, int gby, bool vig,
-		const char* png_path, bool resident) {
-	st.resident_views = resident;
-	st.gain_compensation = gain;
-	st.vignetting = vig;
-	st.gain_blocks_x = gbx; st.gain_blocks_y = gby;
+static int run_build(Stitcher& st, const Options& o) {
+	st.resident_views = o.resident;
+	st.gain_compensation = o.compensation.gain;
+	st.vignetting = o.compensation.vignetting;
+	st.gain_blocks_x = o.compensation.bx; st.gain_blocks_y = o.compensation.by;
 	Mat32f pano = st.build();
-	FILE* fo = fopen(out_path, "wb");
-	if (!fo) { perror(out_path); return 2; }
-	put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
-	put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
+	FILE* fo = fopen(o.out_path, "wb");
+	if (!fo) { perror(o.out_path); return 2; }
+	put_mat(fo, pano);
 	put(fo, st.gains.data(), st.gains.size());
-	if (vig) put(fo, st.vignette_poly.data(), 3);
+	if (st.vignetting) put(fo, st.vignette_poly.data(), 3);
 	fclose(fo);
-	if (png_path) hip_write_png(png_path, pano);
-	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
+	write_files(o, pano);
 	fprintf(stderr, "Final Image Size: (%d, %d), %zu gains\n", pano.cols(), pano.rows(), st.gains.size());
 	return 0;
 }
 
 // CylinderStitcher::build() (stitch/cylstitcher.cc:20-29), stage by stage so that every intermediate can be written out
-static void put_canvas(FILE* fo, const op_canvas* cv) {
-	int h, w;
-	PANO_HIP_CHECK(op_canvas_dims(cv, &h, &w));
-	std::vector<float> px((size_t)h * w * 3);
-	if (!px.empty()) PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), cv, px.data()));
-	put1<int32_t>(fo, h); put1<int32_t>(fo, w);
-	put(fo, px.data(), px.size());
-}
-static int run_cylinder_mode(CylinderStitcher& st, const char* out_path, const char* png_path, bool resident, bool crop) {
-	st.resident_views = resident;
-	FILE* fo = fopen(out_path, "wb");
-	if (!fo) { perror(out_path); return 2; }
+static int run_cylinder_mode(CylinderStitcher& st, const Options& o) {
+	st.resident_views = o.resident;
+	FILE* fo = fopen(o.out_path, "wb");
+	if (!fo) { perror(o.out_path); return 2; }
 	const int n = (int)st.imgs.size();
 	st.calc_feature();
 	put1<int32_t>(fo, n);
@@ -215,60 +213,44 @@ static int run_cylinder_mode(CylinderStitcher& st, const char* out_path, const c
 	for (auto& c : st.bundle.component) put(fo, c.homo.data, 9);
 	st.bundle.proj_method = ConnectedImages::flat;
 	st.bundle.update_proj_range();
-	op_canvas* blended = st.blend();
-	put_canvas(fo, blended);
-	op_canvas* pano = st.perspective_correction(blended);
-	op_canvas_free(blended);
+	HipCanvas blended(st.blend());
+	put_canvas(fo, blended.get());
+	HipCanvas pano(st.perspective_correction(blended.get()));
+	blended.reset();
 	put(fo, st.corners, 8);
 	put(fo, st.inv, 9);
-	put_canvas(fo, pano);
+	put_canvas(fo, pano.get());
 	fclose(fo);
 	int h, w;
-	PANO_HIP_CHECK(op_canvas_dims(pano, &h, &w));
+	PANO_HIP_CHECK(op_canvas_dims(pano.get(), &h, &w));
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", w, h);
-	if (crop) {
-		op_canvas* cc = nullptr;
-		PANO_HIP_CHECK(op_canvas_crop(HipContext::get(), pano, &cc, nullptr, nullptr));
-		op_canvas_free(pano);
-		pano = cc;
-		PANO_HIP_CHECK(op_canvas_dims(pano, &h, &w));
+	if (o.crop) {
+		hip_crop_in_place(pano);
+		PANO_HIP_CHECK(op_canvas_dims(pano.get(), &h, &w));
 		fprintf(stderr, "Cropped Image Size: (%d, %d)\n", w, h);
 	}
-	if (png_path) hip_write_png(png_path, pano);
-	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
-	op_canvas_free(pano);
+	write_files(o, pano.get());
 	return 0;
 }
 
-static void put_mat(FILE* fo, const Mat32f& m) {
-	put1<int32_t>(fo, m.rows()); put1<int32_t>(fo, m.cols());
-	put(fo, m.ptr(), (size_t)m.rows() * m.cols() * 3);
-}
 // CylinderStitcher::build() as a client calls it: build(), the reference's own perspective_correction(Mat32f) on the blend
 // that build left, then build_canvas(crop) on the same object for the files
-static int run_cylinder_build(CylinderStitcher& st, const char* out_path, const char* png_path, bool resident, bool crop, bool profile) {
-	st.resident_views = resident;
-	FILE* fo = fopen(out_path, "wb");
-	if (!fo) { perror(out_path); return 2; }
+static int run_cylinder_build(CylinderStitcher& st, const Options& o) {
+	st.resident_views = o.resident;
+	FILE* fo = fopen(o.out_path, "wb");
+	if (!fo) { perror(o.out_path); return 2; }
 	Mat32f pano = st.build();
 	put_mat(fo, pano);
 	fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
-	{	// the hook for the reference's source: a blended Mat32f in, the corrected one out
-		op_canvas* blended = st.blend();
-		int h, w;
-		PANO_HIP_CHECK(op_canvas_dims(blended, &h, &w));
-		Mat32f ret(h, w, 3);
-		PANO_HIP_CHECK(op_canvas_copy(HipContext::get(), blended, ret.ptr()));
-		op_canvas_free(blended);
-		put_mat(fo, hip_perspective_correction(st.bundle, ret));
-	}
+	// the hook for the reference's source: a blended Mat32f in, the corrected one out
+	put_mat(fo, hip_perspective_correction(st.bundle, hip_canvas_to_mat(HipCanvas(st.blend()))));
 	op_ctx* ctx = HipContext::get();
-	if (profile) { PANO_HIP_CHECK(op_ctx_set_profiling(ctx, 1)); PANO_HIP_CHECK(op_ctx_profile_reset(ctx)); }
+	if (o.profile) { PANO_HIP_CHECK(op_ctx_set_profiling(ctx, 1)); PANO_HIP_CHECK(op_ctx_profile_reset(ctx)); }
 	const auto t0 = std::chrono::steady_clock::now();
-	op_canvas* cv = st.build_canvas(crop);
+	HipCanvas cv(st.build_canvas(o.crop));
 	PANO_HIP_CHECK(op_ctx_sync(ctx));
 	const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	if (profile) {	// the context's stages (HIP events; those labelled "(host)" are host clocks), then their sums and the call's wall time
+	if (o.profile) {	// the context's stages (HIP events; those labelled "(host)" are host clocks), then their sums and the call's wall time
 		double dev = 0, host = 0;
 		for (int i = 0; i < op_ctx_profile_count(ctx); ++i) {
 			const char* label; double ms; long calls;
@@ -279,71 +261,68 @@ static int run_cylinder_build(CylinderStitcher& st, const char* out_path, const 
 		fprintf(stderr, "build_canvas: %.4f ms device stages, %.4f ms host stages, %.4f ms wall\n", dev, host, wall_ms);
 		PANO_HIP_CHECK(op_ctx_set_profiling(ctx, 0));
 	}
-	put_canvas(fo, cv);
+	put_canvas(fo, cv.get());
 	fclose(fo);
-	if (png_path) hip_write_png(png_path, cv);
-	if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, cv, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
-	op_canvas_free(cv);
+	write_files(o, cv.get());
 	return 0;
 }
 
+static int run_camera(Stitcher& st, const Options& o) { return o.mode == "camera_build" ? run_build(st, o) : run_camera_mode(st, o); }
+static int run_cylinder(CylinderStitcher& st, const Options& o) { return o.mode == "cylinder_build" ? run_cylinder_build(st, o) : run_cylinder_mode(st, o); }
+
 int main(int argc, char** argv) {
-	bool gain = false;
-	int gbx = 1, gby = 1;
-	bool vig = false;
-	const char* png_path = nullptr;
-	bool resident = false;
-	const char* jpeg_list = nullptr;
-	bool jpeg_orient = false;
-	bool crop = false, profile = false;
+	Options o;
+	HipCompensation& how = o.compensation;
 	{	// --gain-compensation / --gain-blocks BXxBY may stand anywhere; the positional arguments keep their places
 		int m = 1;
 		for (int k = 1; k < argc; ++k) {
-			if (std::string(argv[k]) == "--gain-compensation") gain = true;
-			else if (std::string(argv[k]) == "--vignetting") vig = true;
-			else if (std::string(argv[k]) == "--resident-views") resident = true;
-			else if (std::string(argv[k]) == "--jpeg-list" && k + 1 < argc) { jpeg_list = argv[++k]; resident = true; }
-			else if (std::string(argv[k]) == "--jpeg-orient") jpeg_orient = true;
-			else if (std::string(argv[k]) == "--crop") crop = true;
-			else if (std::string(argv[k]) == "--profile") profile = true;
-			else if (std::string(argv[k]) == "--png" && k + 1 < argc) png_path = argv[++k];
-			else if (std::string(argv[k]) == "--jpeg" && k + 1 < argc) g_jpeg_path = argv[++k];
-			else if (std::string(argv[k]) == "--jpeg-444") g_jpeg_444 = true;
+			if (std::string(argv[k]) == "--gain-compensation") how.gain = true;
+			else if (std::string(argv[k]) == "--vignetting") how.vignetting = true;
+			else if (std::string(argv[k]) == "--resident-views") o.resident = true;
+			else if (std::string(argv[k]) == "--jpeg-list" && k + 1 < argc) { o.jpeg_list = argv[++k]; o.resident = true; }
+			else if (std::string(argv[k]) == "--jpeg-orient") o.jpeg_orient = true;
+			else if (std::string(argv[k]) == "--crop") o.crop = true;
+			else if (std::string(argv[k]) == "--profile") o.profile = true;
+			else if (std::string(argv[k]) == "--png" && k + 1 < argc) o.png_path = argv[++k];
+			else if (std::string(argv[k]) == "--jpeg" && k + 1 < argc) o.jpeg_path = argv[++k];
+			else if (std::string(argv[k]) == "--jpeg-444") o.jpeg_444 = true;
 			else if (std::string(argv[k]) == "--jpeg-quality" && k + 1 < argc) {
-				if (sscanf(argv[++k], "%d", &g_jpeg_quality) != 1 || g_jpeg_quality < 1 || g_jpeg_quality > 100) {
+				if (sscanf(argv[++k], "%d", &o.jpeg_quality) != 1 || o.jpeg_quality < 1 || o.jpeg_quality > 100) {
 					fprintf(stderr, "--jpeg-quality wants an integer in [1, 100]; got %s\n", argv[k]); return 2;
 				}
 			}
 			else if (std::string(argv[k]) == "--gain-blocks" && k + 1 < argc) {
-				if (sscanf(argv[++k], "%dx%d", &gbx, &gby) != 2 || gbx < 1 || gbx > 16 || gby < 1 || gby > 16) {
+				if (sscanf(argv[++k], "%dx%d", &how.bx, &how.by) != 2 || how.bx < 1 || how.bx > 16 || how.by < 1 || how.by > 16) {
 					fprintf(stderr, "--gain-blocks wants BXxBY, each in [1, 16]; got %s\n", argv[k]); return 2;
 				}
-				gain = true;
+				how.gain = true;
 			}
 			else argv[m++] = argv[k];
 		}
 		argc = m;
 	}
-	if (vig && gbx * gby > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
+	if (how.vignetting && how.bx * how.by > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
 	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build|cylinder|cylinder_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH [--jpeg-orient]] [--crop] [--profile]\n", argv[0]); return 2; }
-	if (jpeg_orient && !jpeg_list) { fprintf(stderr, "--jpeg-orient goes with --jpeg-list\n"); return 2; }
-	const uint32_t base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
-	const std::string mode = argc > 4 ? argv[4] : "";
+	if (o.jpeg_orient && !o.jpeg_list) { fprintf(stderr, "--jpeg-orient goes with --jpeg-list\n"); return 2; }
+	o.out_path = argv[2];
+	o.base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
+	o.mode = argc > 4 ? argv[4] : "";
+	const std::string& mode = o.mode;
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
 	const bool cylinder_mode = mode == "cylinder" || mode == "cylinder_build";
 	if (cylinder_mode) {
-		if (gain || vig) { fprintf(stderr, "cylinder mode takes no gain or vignetting compensation\n"); return 2; }
+		if (how.gain || how.vignetting) { fprintf(stderr, "cylinder mode takes no gain or vignetting compensation\n"); return 2; }
 		config::CYLINDER = true; config::ESTIMATE_CAMERA = false; config::TRANS = false; config::ORDERED_INPUT = true;
 	}
-	if (crop && !cylinder_mode) { fprintf(stderr, "--crop goes with cylinder\n"); return 2; }
-	if (profile && mode != "cylinder_build") { fprintf(stderr, "--profile goes with cylinder_build\n"); return 2; }
-	if (jpeg_list) {
+	if (o.crop && !cylinder_mode) { fprintf(stderr, "--crop goes with cylinder\n"); return 2; }
+	if (o.profile && mode != "cylinder_build") { fprintf(stderr, "--profile goes with cylinder_build\n"); return 2; }
+	if (o.jpeg_list) {
 		if (!camera_mode && !cylinder_mode) { fprintf(stderr, "--jpeg-list goes with camera, camera_ordered, camera_build or cylinder\n"); return 2; }
 		std::vector<std::string> paths;
-		FILE* fl = fopen(jpeg_list, "r");
-		if (!fl) { perror(jpeg_list); return 2; }
+		FILE* fl = fopen(o.jpeg_list, "r");
+		if (!fl) { perror(o.jpeg_list); return 2; }
 		char line[4096];
 		while (fgets(line, sizeof line, fl)) {
 			std::string p(line);
@@ -352,13 +331,11 @@ int main(int argc, char** argv) {
 		}
 		fclose(fl);
 		if (cylinder_mode) {
-			CylinderStitcher st(paths, base_seed, jpeg_orient);
-			if (mode == "cylinder_build") return run_cylinder_build(st, argv[2], png_path, resident, crop, profile);
-			return run_cylinder_mode(st, argv[2], png_path, resident, crop);
+			CylinderStitcher st(paths, o.base_seed, o.jpeg_orient);
+			return run_cylinder(st, o);
 		}
-		Stitcher st(paths, base_seed, jpeg_orient);
-		if (mode == "camera_build") return run_build(st, argv[2], gain, gbx, gby, vig, png_path, resident);
-		return run_camera_mode(st, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
+		Stitcher st(paths, o.base_seed, o.jpeg_orient);
+		return run_camera(st, o);
 	}
 	FILE* fi = fopen(argv[1], "rb");
 	if (!fi) { perror(argv[1]); return 2; }
@@ -372,14 +349,12 @@ int main(int argc, char** argv) {
 	}
 	fclose(fi);
 	if (cylinder_mode) {
-		CylinderStitcher st(mats, base_seed);
-		if (mode == "cylinder_build") return run_cylinder_build(st, argv[2], png_path, resident, crop, profile);
-		return run_cylinder_mode(st, argv[2], png_path, resident, crop);
+		CylinderStitcher st(mats, o.base_seed);
+		return run_cylinder(st, o);
 	}
 	if (camera_mode) {
-		Stitcher st(mats, base_seed);
-		if (mode == "camera_build") return run_build(st, argv[2], gain, gbx, gby, vig, png_path, resident);
-		return run_camera_mode(st, argv[2], base_seed, mode == "camera_ordered", gain, gbx, gby, vig, png_path, resident);
+		Stitcher st(mats, o.base_seed);
+		return run_camera(st, o);
 	}
 
 	// ---- StitcherBase::calc_feature (stitch/stitcherbase.cc:9-27)
@@ -388,15 +363,10 @@ int main(int argc, char** argv) {
 	SIFTDetector feature_det;
 	std::vector<const Mat32f*> ptrs;
 	for (auto& r : imgs) ptrs.push_back(r.img);
-	HipFeatureSet fs = feature_det.calc_feature(ptrs, resident);
-	FILE* fo = fopen(argv[2], "wb");
-	if (!fo) { perror(argv[2]); return 2; }
-	for (int k = 0; k < n; ++k) {
-		put1<int32_t>(fo, (int32_t)fs.feats[k].size());
-		for (auto& d : fs.feats[k]) put(fo, d.descriptor.data(), 128);
-		for (auto& d : fs.feats[k]) { double c[2] = {d.coor.x, d.coor.y}; put(fo, c, 2); }
-		fprintf(stderr, "Image %d has %zu features\n", k, fs.feats[k].size());
-	}
+	HipFeatureSet fs = feature_det.calc_feature(ptrs, o.resident);
+	FILE* fo = fopen(o.out_path, "wb");
+	if (!fo) { perror(o.out_path); return 2; }
+	put_features(fo, fs);
 
 	// ---- Stitcher::linear_pairwise_match (stitch/stitcher.cc:115-136): (i, i+1) for an ordered input
 	std::vector<std::pair<int, int>> tasks;
@@ -405,21 +375,8 @@ int main(int argc, char** argv) {
 	for (auto& r : imgs) shapes.push_back(r.shape());
 	PairWiseMatcher pwmatcher(fs);
 	pwmatcher.precompute(tasks);
-	auto infos = hip_match_images(fs, shapes, tasks, base_seed);
-	put1<int32_t>(fo, (int32_t)tasks.size());
-	for (size_t p = 0; p < tasks.size(); ++p) {
-		MatchData md = pwmatcher.match(tasks[p].first, tasks[p].second);
-		put1<int32_t>(fo, tasks[p].first); put1<int32_t>(fo, tasks[p].second); put1<int32_t>(fo, md.size());
-		for (auto& q : md.data) { int32_t v[2] = {q.first, q.second}; put(fo, v, 2); }
-		const MatchInfo& info = infos[p].second;
-		put1<int32_t>(fo, infos[p].first ? 1 : 0); put1<float>(fo, info.confidence);
-		double hh[9]; for (int i = 0; i < 9; ++i) hh[i] = infos[p].first ? info.homo[i] : 0.0;
-		put(fo, hh, 9);
-		put1<int32_t>(fo, (int32_t)(infos[p].first ? info.match.size() : 0));
-		if (infos[p].first) for (auto& m : info.match) { double v[4] = {m.first.x, m.first.y, m.second.x, m.second.y}; put(fo, v, 4); }
-		fprintf(stderr, "pair (%d,%d): %d matches, %s, confidence %g\n", tasks[p].first, tasks[p].second, md.size(),
-				infos[p].first ? "connected" : "rejected", info.confidence);
-	}
+	auto infos = hip_match_images(fs, shapes, tasks, o.base_seed);
+	put_pairs(fo, pwmatcher, tasks, infos);
 
 	// ---- chain to the middle image (stand-in for the host-only camera estimation), then
 	// ConnectedImages::{calc_inverse_homo, update_proj_range, blend} (stitch/stitcher_image.cc)
@@ -427,18 +384,18 @@ int main(int argc, char** argv) {
 	for (auto& r : infos) all = all && r.first;
 	if (all) {
 		ConnectedImages bundle;
-		bundle.views = fs.views;                                    // NULL without --resident-views
+		bundle.views = fs.views.get();                              // NULL without --resident-views
 		bundle.proj_method = ConnectedImages::flat;
 		bundle.identity_idx = n >> 1;                               // stitcher.cc:139
 		std::vector<Homography> to_mid(n, Homography::I());
-		for (int i = bundle.identity_idx + 1; i < n; ++i) to_mid[i] = mul(to_mid[i - 1], infos[i - 1].second.homo);     // H(i -> i-1)
+		for (int i = bundle.identity_idx + 1; i < n; ++i) to_mid[i] = to_mid[i - 1] * infos[i - 1].second.homo;     // H(i -> i-1)
 		// images left of the middle need the inverse direction: invert through the C-ABI's host helper
 		for (int i = bundle.identity_idx - 1; i >= 0; --i) {
 			const op_config cfg = hip_config_snapshot();
 			double hinv[9], rng[4]; op_blend_geom g; int sh[2] = {w, h};
 			PANO_HIP_CHECK(op_blend_prepare(&cfg, 0, 0, 1, sh, infos[i].second.homo.data, &g, hinv, rng));
 			Homography inv; for (int k = 0; k < 9; ++k) inv[k] = hinv[k];
-			to_mid[i] = mul(to_mid[i + 1], inv);
+			to_mid[i] = to_mid[i + 1] * inv;
 		}
 		for (int i = 0; i < n; ++i) {
 			bundle.component.emplace_back(&imgs[i]);
@@ -446,19 +403,15 @@ int main(int argc, char** argv) {
 		}
 		bundle.calc_inverse_homo();
 		bundle.update_proj_range();
-		const bool blocks = gain && gbx * gby > 1;
-		std::array<float, 3> poly = {0.f, 0.f, 0.f};
-		const std::vector<float> gains = vig ? hip_vignette_compensate(bundle, poly) : blocks ? hip_gain_compensate_blocks(bundle, gbx, gby)
-		                               : gain ? hip_gain_compensate(bundle) : std::vector<float>();
-		Mat32f pano = vig ? hip_blend(bundle, false, gains, poly) : blocks ? hip_blend(bundle, false, gains, gbx, gby) : hip_blend(bundle, false, gains);
-		put1<int32_t>(fo, pano.rows()); put1<int32_t>(fo, pano.cols());
-		put(fo, pano.ptr(), (size_t)pano.rows() * pano.cols() * 3);
+		std::vector<float> gains;
+		std::array<float, 3> poly;
+		Mat32f pano = hip_compensate_and_blend(bundle, how, gains, poly);
+		put_mat(fo, pano);
 		for (auto& t : to_mid) put(fo, t.data, 9);
 		put(fo, gains.data(), gains.size());
-		if (vig) put(fo, poly.data(), 3);
+		if (how.vignetting) put(fo, poly.data(), 3);
 		fprintf(stderr, "Final Image Size: (%d, %d)\n", pano.cols(), pano.rows());
-		if (png_path) hip_write_png(png_path, pano);
-		if (g_jpeg_path) hip_write_jpeg(g_jpeg_path, pano, g_jpeg_quality, g_jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
+		write_files(o, pano);
 	} else {
 		put1<int32_t>(fo, 0); put1<int32_t>(fo, 0);
 	}
