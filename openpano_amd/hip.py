@@ -63,6 +63,147 @@ class OpBlendGeom(C.Structure):
                 ("resolution", C.c_double * 2)]
 
 
+# The prototypes of include/openpano_hip.h, in the header's order: name -> (restype, argtypes).  lib() binds exactly these and
+# refuses a library that lacks one; tests/test_binding_header_cpu.py holds the table against the header.  Handles and array
+# arguments are c_void_p (see _p), out-parameters for scalars and the structs are typed pointers.
+_V, _S, _I, _I64, _U32, _F, _D = C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_double
+_PV, _PS, _PI, _PI64 = C.POINTER(_V), C.POINTER(_S), C.POINTER(_I), C.POINTER(_I64)
+_CFG, _IMG, _BIMG, _GEOM = C.POINTER(OpConfig), C.POINTER(OpImage), C.POINTER(OpBlendImage), C.POINTER(OpBlendGeom)
+_BLEND = [_V, _CFG, _GEOM, _BIMG, _I]        # ctx, cfg, geometry, images, n: how every blend and overlap call starts
+_RANSAC = [_V, _CFG, _V, _V, _V, _I, _V, _V, _U32, _PV]
+
+PROTOTYPES = {
+    "op_last_error": (_S, []),
+    "op_abi_version": (_I, []),
+    # configuration
+    "op_config_default": (None, [_CFG]),
+    # context
+    "op_ctx_create": (_I, [_I, _V, _PV]),
+    "op_ctx_destroy": (None, [_V]),
+    "op_ctx_sync": (_I, [_V]),
+    "op_ctx_set_profiling": (_I, [_V, _I]),
+    "op_ctx_profile_only": (_I, [_V, _S]),
+    "op_ctx_profile_reset": (_I, [_V]),
+    "op_ctx_profile_count": (_I, [_V]),
+    "op_ctx_profile_get": (_I, [_V, _I, _PS, C.POINTER(_D), C.POINTER(C.c_long)]),
+    # SIFT
+    "op_sift_batch": (_I, [_V, _CFG, _IMG, _I, _PV]),
+    "op_sift_batch_host": (_I, [_V, _CFG, _IMG, _I, _V, _V, _I64, _PV]),
+    "op_features_num_images": (_I, [_V]),
+    "op_features_count": (_I, [_V, _I]),
+    "op_features_offset": (_I64, [_V, _I]),
+    "op_features_total": (_I64, [_V]),
+    "op_features_desc_device": (_V, [_V]),
+    "op_features_coor_device": (_V, [_V]),
+    "op_features_copy": (_I, [_V, _V, _I, _V, _V]),
+    "op_features_copy_real": (_I, [_V, _V, _I, _V]),
+    "op_features_from_host": (_I, [_V, _PV, _PV, _PI, _I, _PV]),
+    "op_features_from_device": (_I, [_V, _V, _V, _PI, _I, _PV]),
+    "op_features_adopt_device": (_I, [_V, _V, _V, _PI, _I, _PV]),
+    "op_features_free": (None, [_V]),
+    # staged single-image run
+    "op_sift_staged": (_I, [_V, _CFG, _IMG, _PV]),
+    "op_sift_dump_free": (None, [_V]),
+    "op_sift_dump_working_dims": (_I, [_V, _PI, _PI]),
+    "op_sift_dump_octave_dims": (_I, [_V, _I, _PI, _PI]),
+    "op_sift_dump_plane": (_I, [_V, _V, _I, _I, _I, _V]),
+    "op_sift_dump_raw_count": (_I, [_V, _I, _I]),
+    "op_sift_dump_raw": (_I, [_V, _I, _I, _V]),
+    "op_sift_dump_kp_count": (_I, [_V, _I]),
+    "op_sift_dump_kp": (_I, [_V, _I, _V, _V, _V]),
+    "op_sift_dump_desc": (_I, [_V, _V, _V]),
+    # test hooks
+    "op_debug_math": (_I, [_V, _I, _V, _V, _I, _V]),
+    "op_debug_set_raw_capacity": (_I, [_V, _I]),
+    "op_debug_set_desc_list_cap": (_I, [_V, _I]),
+    "op_debug_pool_stats": (_I, [_PI64, _PI64, _PI64]),
+    # match
+    "op_match_pairs": (_I, [_V, _CFG, _V, _V, _I, _PV]),
+    "op_matches_count": (_I, [_V, _I]),
+    "op_matches_copy": (_I, [_V, _I, _V]),
+    "op_matches_copy_all": (_I, [_V, _V, _V]),
+    "op_matches_device_list": (_V, [_V]),
+    "op_matches_total": (_I64, [_V]),
+    "op_matches_from_host": (_I, [_PV, _PI, _I, _PV]),
+    "op_matches_concat": (_I, [_V, _V, _V, _PV]),
+    "op_matches_free": (None, [_V]),
+    # several GPUs in one process
+    "op_group_create": (_I, [_PI, _I, _PV]),
+    "op_group_destroy": (None, [_V]),
+    "op_group_size": (_I, [_V]),
+    "op_group_ctx": (_V, [_V, _I]),
+    "op_sift_batch_multi": (_I, [_V, _CFG, _IMG, _I, _PV]),
+    "op_match_pairs_multi": (_I, [_V, _CFG, _V, _V, _I, _PV]),
+    "op_ransac_pairs_multi": (_I, _RANSAC),
+    # RANSAC
+    "op_ransac_pairs": (_I, _RANSAC),
+    "op_ransac_ok": (_I, [_V, _I]),
+    "op_ransac_confidence": (_F, [_V, _I]),
+    "op_ransac_homo": (_I, [_V, _I, _V]),
+    "op_ransac_inlier_count": (_I, [_V, _I]),
+    "op_ransac_inliers": (_I, [_V, _I, _V]),
+    "op_ransac_best": (_I, [_V, _I, _PI, _PI]),
+    "op_ransac_summary": (_I, [_V, _PI, _PI64]),
+    "op_ransac_free": (None, [_V]),
+    "op_pairwise_table_size": (_I, [_V, _PI, _PI64]),
+    "op_pairwise_table": (_I, [_V, _V, _V, _V, _V, _I, _V, _V, _V, _V, _V]),
+    # warp + blend
+    "op_blend_prepare": (_I, [_CFG, _I, _I, _I, _V, _V, _GEOM, _V, _V]),
+    "op_blend_canvas_dims": (_I, [_GEOM, _BIMG, _I, _PI, _PI]),
+    "op_blend": (_I, _BLEND + [_PV]),
+    "op_canvas_dims": (_I, [_V, _PI, _PI]),
+    "op_canvas_device": (_V, [_V]),
+    "op_canvas_copy": (_I, [_V, _V, _V]),
+    "op_canvas_free": (None, [_V]),
+    "op_canvas_crop": (_I, [_V, _V, _PV, _PI, _PI]),
+    "op_canvas_copy_u8": (_I, [_V, _V, _V]),
+    # exposure (gain) compensation
+    "op_gain_overlap": (_I, _BLEND + [_I, _V, _V]),
+    "op_gain_solve": (_I, [_I, _V, _V, _D, _D, _I, _V]),
+    "op_blend_gains": (_I, _BLEND + [_V, _PV]),
+    # block gain compensation
+    "op_gain_block_overlap": (_I, _BLEND + [_I, _I, _I, _V, _V]),
+    "op_gain_block_solve": (_I, [_I, _I, _I, _V, _V, _D, _D, _D, _I, _V]),
+    "op_blend_block_gains": (_I, _BLEND + [_I, _I, _V, _PV]),
+    # vignetting compensation
+    "op_vignette_overlap": (_I, _BLEND + [_I, _F, _V, _V]),
+    "op_vignette_solve": (_I, [_I, _V, _V, _I, _D, _D, _D, _V, _V]),
+    "op_blend_vignette": (_I, _BLEND + [_V, _V, _PV]),
+    # PNG output
+    "op_canvas_encode_png": (_I, [_V, _V, _PV]),
+    "op_png_encode_u8": (_I, [_V, _V, _I, _I, _PV]),
+    "op_png_size": (_I64, [_V]),
+    "op_png_copy": (_I, [_V, _V, _V]),
+    "op_png_free": (None, [_V]),
+    # JPEG output
+    "op_canvas_encode_jpeg": (_I, [_V, _V, _I, _I, _PV]),
+    "op_jpeg_encode_u8": (_I, [_V, _V, _I, _I, _I, _I, _PV]),
+    "op_jpeg_size": (_I64, [_V]),
+    "op_jpeg_copy": (_I, [_V, _V, _V]),
+    "op_jpeg_free": (None, [_V]),
+    # CYLINDER mode: pre-warp, perspective correction
+    "op_cyl_warp_shape": (_I, [_CFG, _I, _I, _D, _V, _I, _PI, _PI, _V]),
+    "op_cyl_warp": (_I, [_V, _CFG, _IMG, _D, _PV]),
+    "op_canvas_upload": (_I, [_V, _V, _I, _I, _PV]),
+    "op_perspective_homography": (_I, [_GEOM, _I, _I, _I, _I, _V, _I, _I, _V, _I, _I, _V, _V]),
+    "op_canvas_perspective": (_I, [_V, _CFG, _V, _V, _PV]),
+    # resident views
+    "op_views_upload": (_I, [_V, _IMG, _I, _PV]),
+    "op_views_count": (_I, [_V]),
+    "op_views_image": (_I, [_V, _I, _IMG]),
+    "op_views_blend_image": (_I, [_V, _I, _BIMG]),
+    "op_views_free": (None, [_V]),
+    # JPEG input (files travel as bytes: c_char_p)
+    "op_jpeg_probe": (_I, [_S, _I64, _PI, _PI, _PI]),
+    "op_views_decode_jpeg": (_I, [_V, _PS, _PI64, _I, _PV]),
+    "op_views_copy": (_I, [_V, _V, _I, _V]),
+    "op_debug_set_jpeg_subseq_bits": (_I, [_V, _I]),
+    "op_debug_jpeg_last_rounds": (_I, [_V]),
+    # EXIF orientation
+    "op_jpeg_exif": (_I, [_S, _I64, _PI, _PI]),
+    "op_views_decode_jpeg_oriented": (_I, [_V, _PS, _PI64, _I, _PI, _PV]),
+}
+
 _lib = None
 
 
@@ -91,7 +232,7 @@ def _bind_torch_hip_runtime():
 
 
 def lib():
-    """Load the HIP library (once). Raises if it has not been built -- no CPU fallback."""
+    """Load the HIP library (once). Raises if it has not been built -- no CPU fallback -- or lacks an entry point of PROTOTYPES."""
     global _lib
     if _lib is not None:
         return _lib
@@ -101,170 +242,88 @@ def lib():
             "or `make -C openpano_amd/csrc`; openpano_amd has no CPU fallback")
     _bind_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    L.op_last_error.restype = C.c_char_p
-    L.op_abi_version.restype = C.c_int
-    L.op_config_default.argtypes = [C.POINTER(OpConfig)]
-    L.op_ctx_create.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-    L.op_ctx_destroy.argtypes = [C.c_void_p]
-    L.op_ctx_sync.argtypes = [C.c_void_p]
-    L.op_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    if hasattr(L, "op_ctx_profile_only"):
-        L.op_ctx_profile_only.argtypes = [C.c_void_p, C.c_char_p]
-    L.op_ctx_profile_reset.argtypes = [C.c_void_p]
-    L.op_ctx_profile_count.argtypes = [C.c_void_p]
-    L.op_ctx_profile_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_long)]
-    L.op_sift_batch.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_int, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_sift_batch_host"):
-        L.op_sift_batch_host.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
-    L.op_features_num_images.argtypes = [C.c_void_p]
-    L.op_features_count.argtypes = [C.c_void_p, C.c_int]
-    L.op_features_offset.restype = C.c_int64
-    L.op_features_offset.argtypes = [C.c_void_p, C.c_int]
-    L.op_features_total.restype = C.c_int64
-    L.op_features_total.argtypes = [C.c_void_p]
-    L.op_features_desc_device.restype = C.c_void_p
-    L.op_features_desc_device.argtypes = [C.c_void_p]
-    L.op_features_coor_device.restype = C.c_void_p
-    L.op_features_coor_device.argtypes = [C.c_void_p]
-    L.op_features_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.op_features_copy_real.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.op_features_from_host.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
-    L.op_features_from_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_features_adopt_device"):
-        L.op_features_adopt_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
-    L.op_features_free.argtypes = [C.c_void_p]
-    L.op_sift_staged.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.POINTER(C.c_void_p)]
-    L.op_sift_dump_free.argtypes = [C.c_void_p]
-    L.op_sift_dump_working_dims.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.op_sift_dump_octave_dims.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.op_sift_dump_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.op_sift_dump_raw_count.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.op_sift_dump_raw.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.op_sift_dump_kp_count.argtypes = [C.c_void_p, C.c_int]
-    L.op_sift_dump_kp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.op_sift_dump_desc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.op_debug_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.op_debug_set_raw_capacity.argtypes = [C.c_void_p, C.c_int]
-    L.op_debug_set_desc_list_cap.argtypes = [C.c_void_p, C.c_int]
-    L.op_debug_pool_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    if hasattr(L, "op_match_pairs"):
-        L.op_match_pairs.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-        L.op_matches_count.argtypes = [C.c_void_p, C.c_int]
-        L.op_matches_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        if hasattr(L, "op_matches_copy_all"):
-            L.op_matches_copy_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "op_matches_device_list"):
-            L.op_matches_device_list.restype = C.c_void_p
-        if hasattr(L, "op_matches_device_list"):
-            L.op_matches_device_list.argtypes = [C.c_void_p]
-        L.op_matches_total.restype = C.c_int64
-        L.op_matches_total.argtypes = [C.c_void_p]
-        L.op_matches_free.argtypes = [C.c_void_p]
-    L.op_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
-    L.op_group_destroy.argtypes = [C.c_void_p]
-    L.op_group_size.argtypes = [C.c_void_p]
-    L.op_group_ctx.restype = C.c_void_p
-    L.op_group_ctx.argtypes = [C.c_void_p, C.c_int]
-    L.op_sift_batch_multi.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_int, C.POINTER(C.c_void_p)]
-    L.op_match_pairs_multi.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_ransac_pairs_multi"):
-        L.op_ransac_pairs_multi.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
-    L.op_matches_from_host.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_matches_concat"):
-        L.op_matches_concat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    L.op_ransac_pairs.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                  C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
-    L.op_ransac_ok.argtypes = [C.c_void_p, C.c_int]
-    L.op_ransac_confidence.restype = C.c_float
-    L.op_ransac_confidence.argtypes = [C.c_void_p, C.c_int]
-    L.op_ransac_homo.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.op_ransac_inlier_count.argtypes = [C.c_void_p, C.c_int]
-    L.op_ransac_inliers.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.op_ransac_best.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    if hasattr(L, "op_ransac_summary"):
-        L.op_ransac_summary.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
-    L.op_ransac_free.argtypes = [C.c_void_p]
-    if hasattr(L, "op_pairwise_table"):
-        L.op_pairwise_table_size.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
-        L.op_pairwise_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.op_blend_prepare.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                   C.POINTER(OpBlendGeom), C.c_void_p, C.c_void_p]
-    L.op_blend_canvas_dims.argtypes = [C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.op_blend.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int, C.POINTER(C.c_void_p)]
-    L.op_canvas_dims.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.op_canvas_device.restype = C.c_void_p
-    L.op_canvas_device.argtypes = [C.c_void_p]
-    L.op_canvas_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.op_canvas_free.argtypes = [C.c_void_p]
-    L.op_canvas_crop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.op_canvas_copy_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "op_gain_overlap"):
-        L.op_gain_overlap.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int, C.c_int,
-                                      C.c_void_p, C.c_void_p]
-        L.op_gain_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]
-        L.op_blend_gains.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
-                                     C.c_void_p, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_gain_block_overlap"):
-        L.op_gain_block_overlap.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
-                                            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.op_gain_block_solve.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
-                                          C.c_int, C.c_void_p]
-        L.op_blend_block_gains.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
-                                           C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_vignette_overlap"):
-        L.op_vignette_overlap.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
-                                          C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-        L.op_vignette_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
-                                        C.c_void_p]
-        L.op_blend_vignette.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpBlendGeom), C.POINTER(OpBlendImage), C.c_int,
-                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_canvas_encode_png"):
-        L.op_canvas_encode_png.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-        L.op_png_encode_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.op_png_size.restype = C.c_int64
-        L.op_png_size.argtypes = [C.c_void_p]
-        L.op_png_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.op_png_free.argtypes = [C.c_void_p]
-    if hasattr(L, "op_canvas_encode_jpeg"):
-        L.op_canvas_encode_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.op_jpeg_encode_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.op_jpeg_size.restype = C.c_int64
-        L.op_jpeg_size.argtypes = [C.c_void_p]
-        L.op_jpeg_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.op_jpeg_free.argtypes = [C.c_void_p]
-    L.op_cyl_warp_shape.argtypes = [C.POINTER(OpConfig), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
-                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
-    L.op_cyl_warp.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.POINTER(OpImage), C.c_double, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_canvas_perspective"):
-        L.op_canvas_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.op_perspective_homography.argtypes = [C.POINTER(OpBlendGeom), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.op_canvas_perspective.argtypes = [C.c_void_p, C.POINTER(OpConfig), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    if hasattr(L, "op_views_upload"):
-        L.op_views_upload.argtypes = [C.c_void_p, C.POINTER(OpImage), C.c_int, C.POINTER(C.c_void_p)]
-        L.op_views_count.argtypes = [C.c_void_p]
-        L.op_views_image.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpImage)]
-        L.op_views_blend_image.argtypes = [C.c_void_p, C.c_int, C.POINTER(OpBlendImage)]
-        L.op_views_free.argtypes = [C.c_void_p]
-    if hasattr(L, "op_views_decode_jpeg"):
-        L.op_jpeg_probe.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.op_views_decode_jpeg.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_void_p)]
-        L.op_views_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.op_debug_set_jpeg_subseq_bits.argtypes = [C.c_void_p, C.c_int]
-        L.op_debug_jpeg_last_rounds.argtypes = [C.c_void_p]
-    if hasattr(L, "op_views_decode_jpeg_oriented"):
-        L.op_jpeg_exif.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.op_views_decode_jpeg_oriented.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
-                                                    C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
+    missing = []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            missing.append(name)
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
+    if missing:
+        raise OpenPanoHipError(f"{LIB_PATH} does not export {', '.join(missing)}: it was built from another include/openpano_hip.h")
     _lib = L
     return L
+
+
+def use_library(path):
+    """Switch this process to another build of the same ABI (the A/B scripts) -> lib().  Close every context and free every
+    handle of the previous library first."""
+    global _lib, LIB_PATH
+    LIB_PATH = path
+    _lib = None
+    return lib()
 
 
 def check(rc):
     if rc != 0:
         raise OpenPanoHipError(f"libopenpano_hip error {rc}: {lib().op_last_error().decode(errors='replace')}")
+
+
+def _p(a):
+    """a numpy array's data as the c_void_p the table declares for array arguments; None -> NULL"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _pairs(a):
+    """(n, 2) contiguous int32: a list of image pairs (i, j)"""
+    return np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1, 2))
+
+
+_shapes = _pairs        # (n, 2) contiguous int32 just the same: the images' (w, h)
+
+
+def _seeds(seeds):
+    """per-pair RANSAC seeds as contiguous uint32, or None (the library derives them from base_seed)"""
+    return None if seeds is None else np.ascontiguousarray(np.asarray(seeds, np.uint32))
+
+
+def _cfg(cfg):
+    """a config object as the ``const op_config*`` argument of one call"""
+    return C.byref(OpConfig.from_config(cfg))
+
+
+def _new(fn, *args):
+    """fn(*args, &handle), checked -> the handle the library made"""
+    h = C.c_void_p()
+    check(fn(*args, C.byref(h)))
+    return h
+
+
+def _write(path, data):
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+class _Handle:
+    """Owner of one library object: ``handle`` is its pointer, None once freed (the object is then false); ``_free_fn`` names
+    the entry point that releases it."""
+    _free_fn = None
+    handle = None
+
+    def free(self):
+        if self.handle:
+            getattr(lib(), self._free_fn)(self.handle)
+            self.handle = None
+
+    def __bool__(self):
+        return bool(self.handle)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def pool_stats():
@@ -274,12 +333,12 @@ def pool_stats():
     return tuple(x.value for x in v)
 
 
-class Context:
+class Context(_Handle):
     """``op_ctx``: one per (process, device); ``stream`` is an optional raw ``hipStream_t``."""
+    _free_fn = "op_ctx_destroy"
 
     def __init__(self, device: int = 0, stream: int | None = None):
-        self.handle = C.c_void_p()
-        check(lib().op_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(self.handle)))
+        self.handle = _new(lib().op_ctx_create, device, C.c_void_p(stream) if stream else None)
         self.device = device
 
     def sync(self):
@@ -287,10 +346,8 @@ class Context:
 
     def set_profiling(self, enable=True, only=None):
         """per-stage HIP-event timing on this context's stream; only = one stage label to bracket (None: all)"""
-        L = lib()
-        if hasattr(L, "op_ctx_profile_only"):
-            check(L.op_ctx_profile_only(self.handle, only.encode() if only else None))
-        check(L.op_ctx_set_profiling(self.handle, int(enable)))
+        check(lib().op_ctx_profile_only(self.handle, only.encode() if only else None))
+        check(lib().op_ctx_set_profiling(self.handle, int(enable)))
 
     def profile_reset(self):
         check(lib().op_ctx_profile_reset(self.handle))
@@ -322,15 +379,7 @@ class Context:
         check(lib().op_debug_set_raw_capacity(self.handle, int(cap)))
 
     def close(self):
-        if self.handle:
-            lib().op_ctx_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.free()
 
 
 class _BorrowedContext(Context):
@@ -340,58 +389,40 @@ class _BorrowedContext(Context):
         self.handle = C.c_void_p(handle)
         self.device = device
 
-    def close(self):
-        self.handle = C.c_void_p()
+    def free(self):
+        self.handle = None
 
 
-class Group:
+class Group(_Handle):
     """``op_group``: several GPUs driven from this process; a device may be listed twice."""
+    _free_fn = "op_group_destroy"
 
     def __init__(self, devices):
         devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-        self.handle = C.c_void_p()
-        check(lib().op_group_create(devs, len(devices), C.byref(self.handle)))
+        self.handle = _new(lib().op_group_create, devs, len(devices))
         self.devices = list(devices)
         self.ctx0 = _BorrowedContext(lib().op_group_ctx(self.handle, 0), devices[0])
 
     def sift_batch(self, cfg, images) -> "Features":
         arr, keep = _mk_images(images)
-        ccfg = OpConfig.from_config(cfg)
-        h = C.c_void_p()
-        check(lib().op_sift_batch_multi(self.handle, C.byref(ccfg), arr, len(images), C.byref(h)))
+        h = _new(lib().op_sift_batch_multi, self.handle, _cfg(cfg), arr, len(images))
         del keep
         return Features(self.ctx0, h)
 
     def match_pairs_handle(self, cfg, feats, pairs) -> "Matches":
-        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-        ccfg = OpConfig.from_config(cfg)
-        h = C.c_void_p()
-        check(lib().op_match_pairs_multi(self.handle, C.byref(ccfg), feats.handle, pr.ctypes.data_as(C.c_void_p), len(pr), C.byref(h)))
-        return Matches(h, len(pr))
+        return _match(self, cfg, feats, pairs)
 
     def ransac_pairs(self, cfg, feats, matches, pairs, shapes_wh, seeds=None, base_seed=0):
         """op_ransac_pairs_multi -> the same list of dicts as hip.ransac_pairs"""
-        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-        sh = np.ascontiguousarray(np.asarray(shapes_wh, np.int32).reshape(-1, 2))
-        sd = np.ascontiguousarray(np.asarray(seeds, np.uint32)) if seeds is not None else None
-        ccfg = OpConfig.from_config(cfg)
-        h = C.c_void_p()
-        check(lib().op_ransac_pairs_multi(self.handle, C.byref(ccfg), feats.handle, matches.handle, pr.ctypes.data_as(C.c_void_p), len(pr),
-                                          sh.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
-                                          int(base_seed), C.byref(h)))
-        return _unpack_ransac(h, len(pr))
+        return ransac_pairs(self, cfg, feats, matches, pairs, shapes_wh, seeds, base_seed)
+
+    def free(self):
+        if self.handle:
+            self.ctx0.free()
+        super().free()
 
     def close(self):
-        if self.handle:
-            self.ctx0.close()
-            lib().op_group_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.free()
 
 
 def _mk_images(images):
@@ -410,14 +441,15 @@ def _mk_images(images):
             if a.ndim != 3 or a.shape[2] != 3:
                 raise ValueError("image must be H x W x 3 (float32 or uint8)")
             keep.append(a)
-            arr[i] = OpImage(a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], 0, OP_U8 if a.dtype == np.uint8 else OP_F32)
+            arr[i] = OpImage(_p(a), a.shape[0], a.shape[1], 0, OP_U8 if a.dtype == np.uint8 else OP_F32)
     return arr, keep
 
 
-class Views:
+class Views(_Handle):
     """``op_views``: the views of a job uploaded once, each in the type it arrived in (float32, or uint8 decoder bytes),
     resident for ``sift_batch`` / ``cyl_warp`` (``images()``) and for ``blend`` and the overlap passes (pass the object, or
     ``blend_images()``).  The seam of ImageRef::load / img (stitch/imageref.hh:15-31)."""
+    _free_fn = "op_views_free"
 
     def __init__(self, ctx: Context, handle):
         self.ctx = ctx
@@ -428,8 +460,7 @@ class Views:
         """images: as ``sift_batch`` takes them (numpy HWC float32 / uint8, or device tuples); one copy for a
         contiguous stack of host frames"""
         arr, keep = _mk_images(images)
-        h = C.c_void_p()
-        check(lib().op_views_upload(ctx.handle, arr, len(images), C.byref(h)))
+        h = _new(lib().op_views_upload, ctx.handle, arr, len(images))
         del keep
         return cls(ctx, h)
 
@@ -440,17 +471,11 @@ class Views:
         raises, naming its index.
         orient: False: the pixels as stored.  True: every view turned upright by its file's EXIF orientation.  A sequence
         of ints, one per file: 1..8 used as given, 0 = the file's EXIF (op_views_decode_jpeg_oriented)."""
-        if not hasattr(lib(), "op_views_decode_jpeg"):
-            raise OpenPanoHipError("libopenpano_hip.so was built without op_views_decode_jpeg")
         files = [bytes(f) for f in files]
         arr = (C.c_char_p * len(files))(*files)
         sizes = (C.c_int64 * len(files))(*[len(f) for f in files])
-        h = C.c_void_p()
         if orient is False:
-            check(lib().op_views_decode_jpeg(ctx.handle, arr, sizes, len(files), C.byref(h)))
-            return cls(ctx, h)
-        if not hasattr(lib(), "op_views_decode_jpeg_oriented"):
-            raise OpenPanoHipError("libopenpano_hip.so was built without op_views_decode_jpeg_oriented")
+            return cls(ctx, _new(lib().op_views_decode_jpeg, ctx.handle, arr, sizes, len(files)))
         if orient is True:
             how = None
         else:
@@ -458,17 +483,14 @@ class Views:
             if len(orient) != len(files):
                 raise ValueError("orient: one orientation per file")
             how = (C.c_int * len(files))(*orient)
-        check(lib().op_views_decode_jpeg_oriented(ctx.handle, arr, sizes, len(files), how, C.byref(h)))
-        return cls(ctx, h)
+        return cls(ctx, _new(lib().op_views_decode_jpeg_oriented, ctx.handle, arr, sizes, len(files), how))
 
     def numpy(self, i: int) -> np.ndarray:
         """view i read back as (H, W, 3) in its own type, uint8 or float32 (op_views_copy)"""
-        if not hasattr(lib(), "op_views_copy"):
-            raise OpenPanoHipError("libopenpano_hip.so was built without op_views_copy")
         im = OpImage()
         check(lib().op_views_image(self.handle, int(i), C.byref(im)))
         out = np.empty((im.h, im.w, 3), np.uint8 if im.dtype == OP_U8 else np.float32)
-        check(lib().op_views_copy(self.ctx.handle, self.handle, int(i), out.ctypes.data_as(C.c_void_p)))
+        check(lib().op_views_copy(self.ctx.handle, self.handle, int(i), _p(out)))
         return out
 
     @property
@@ -494,17 +516,6 @@ class Views:
             check(lib().op_views_blend_image(self.handle, i, C.byref(arr[i])))
         return arr
 
-    def free(self):
-        if self.handle:
-            lib().op_views_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 JPEG_SAMPLING_NAMES = {0: "444", 1: "420", 2: "422", 3: "grey"}
 
@@ -512,8 +523,6 @@ JPEG_SAMPLING_NAMES = {0: "444", 1: "420", 2: "422", 3: "grey"}
 def jpeg_probe(data):
     """(h, w, sampling) of a JPEG file that ``Views.decode_jpeg`` accepts, sampling one of "444", "422", "420", "grey";
     raises OpenPanoHipError (error -4: outside the format, -1: broken) otherwise.  Host only: needs no device."""
-    if not hasattr(lib(), "op_jpeg_probe"):
-        raise OpenPanoHipError("libopenpano_hip.so was built without op_jpeg_probe")
     data = bytes(data)
     h, w, s = C.c_int(), C.c_int(), C.c_int()
     check(lib().op_jpeg_probe(data, len(data), C.byref(h), C.byref(w), C.byref(s)))
@@ -524,8 +533,6 @@ def jpeg_exif(data):
     """(orientation, focal35) of a JPEG file's EXIF block: orientation 1..8 (1 when absent or unreadable) and
     FocalLengthIn35mmFilm in mm (0 when absent).  Malformed EXIF is no error; only a file without SOI raises.
     Host only: needs no device (op_jpeg_exif)."""
-    if not hasattr(lib(), "op_jpeg_exif"):
-        raise OpenPanoHipError("libopenpano_hip.so was built without op_jpeg_exif")
     data = bytes(data)
     o, f = C.c_int(), C.c_int()
     check(lib().op_jpeg_exif(data, len(data), C.byref(o), C.byref(f)))
@@ -545,8 +552,17 @@ def _mk_blend_images(images):
     return arr, keep
 
 
-class Features:
+class _View:
+    """``__cuda_array_interface__`` over a device buffer of ``owner``, which the view keeps alive"""
+
+    def __init__(self, owner, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr or 0), False), "version": 2, "strides": None}
+        self._owner = owner
+
+
+class Features(_Handle):
     """``op_features``: device-resident descriptors/coordinates of a batch of images."""
+    _free_fn = "op_features_free"
 
     def __init__(self, ctx: Context, handle):
         self.ctx = ctx
@@ -577,39 +593,36 @@ class Features:
     def get(self, i):
         k = self.count(i)
         desc = np.empty((k, 128), np.float32); coor = np.empty((k, 2), np.float64)
-        check(lib().op_features_copy(self.ctx.handle, self.handle, i, desc.ctypes.data_as(C.c_void_p), coor.ctypes.data_as(C.c_void_p)))
+        check(lib().op_features_copy(self.ctx.handle, self.handle, i, _p(desc), _p(coor)))
         return desc, coor
 
     def get_real(self, i):
         """real_coor in [0,1) of image i (what do_detect_feature itself returns, feature.cc:31-47)"""
         k = self.count(i)
         real = np.empty((k, 2), np.float64)
-        check(lib().op_features_copy_real(self.ctx.handle, self.handle, i, real.ctypes.data_as(C.c_void_p)))
+        check(lib().op_features_copy_real(self.ctx.handle, self.handle, i, _p(real)))
         return real
 
     @classmethod
     def from_host(cls, ctx, descs, coors=None):
         n = len(descs)
         descs = [np.ascontiguousarray(d, np.float32).reshape(-1, 128) for d in descs]
-        dp = (C.c_void_p * n)(*[d.ctypes.data_as(C.c_void_p) for d in descs])
+        dp = (C.c_void_p * n)(*[_p(d) for d in descs])
         if coors is not None:
             coors = [np.ascontiguousarray(c, np.float64).reshape(-1, 2) for c in coors]
-            cp = (C.c_void_p * n)(*[c.ctypes.data_as(C.c_void_p) for c in coors])
+            cp = (C.c_void_p * n)(*[_p(c) for c in coors])
         else:
             cp = None
         counts = (C.c_int * n)(*[len(d) for d in descs])
-        h = C.c_void_p()
-        check(lib().op_features_from_host(ctx.handle, dp, cp, counts, n, C.byref(h)))
-        return cls(ctx, h)
+        return cls(ctx, _new(lib().op_features_from_host, ctx.handle, dp, cp, counts, n))
 
     @classmethod
     def from_device(cls, ctx, desc_ptr, counts, coor_ptr=None):
         """flat device buffer (images back to back, total x 128 fp32) -> Features (D2D copy)"""
         n = len(counts)
         cc = (C.c_int * n)(*[int(c) for c in counts])
-        h = C.c_void_p()
-        check(lib().op_features_from_device(ctx.handle, C.c_void_p(int(desc_ptr)), C.c_void_p(int(coor_ptr)) if coor_ptr else None, cc, n, C.byref(h)))
-        return cls(ctx, h)
+        return cls(ctx, _new(lib().op_features_from_device, ctx.handle, C.c_void_p(int(desc_ptr)),
+                             C.c_void_p(int(coor_ptr)) if coor_ptr else None, cc, n))
 
     @classmethod
     def adopt_device(cls, ctx, desc_ptr, counts, coor_ptr, keep=None):
@@ -617,50 +630,23 @@ class Features:
         the memory) is held until free()"""
         n = len(counts)
         cc = (C.c_int * n)(*[int(c) for c in counts])
-        h = C.c_void_p()
-        check(lib().op_features_adopt_device(ctx.handle, C.c_void_p(int(desc_ptr)), C.c_void_p(int(coor_ptr)), cc, n, C.byref(h)))
-        f = cls(ctx, h)
+        f = cls(ctx, _new(lib().op_features_adopt_device, ctx.handle, C.c_void_p(int(desc_ptr)), C.c_void_p(int(coor_ptr)), cc, n))
         f._keep = keep
         return f
 
     def desc_device_array(self):
         """object exposing ``__cuda_array_interface__`` over the device descriptor buffer
         (zero-copy view for torch.as_tensor(..., device='cuda'); valid while self is alive)"""
-        class _View:
-            pass
-        v = _View()
-        v.__cuda_array_interface__ = {"shape": (int(self.total), 128), "typestr": "<f4",
-                                      "data": (int(self.desc_ptr or 0), False), "version": 2, "strides": None}
-        v._owner = self
-        return v
+        return _View(self, self.desc_ptr, (int(self.total), 128), "<f4")
 
     def coor_device_array(self):
         """same for the (total, 2) float64 keypoint coordinates"""
-        class _View:
-            pass
-        v = _View()
-        v.__cuda_array_interface__ = {"shape": (int(self.total), 2), "typestr": "<f8",
-                                      "data": (int(self.coor_ptr or 0), False), "version": 2, "strides": None}
-        v._owner = self
-        return v
-
-    def free(self):
-        if self.handle:
-            lib().op_features_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return _View(self, self.coor_ptr, (int(self.total), 2), "<f8")
 
 
 def sift_batch(ctx: Context, cfg, images) -> Features:
     arr, keep = _mk_images(images)
-    ccfg = OpConfig.from_config(cfg)
-    h = C.c_void_p()
-    check(lib().op_sift_batch(ctx.handle, C.byref(ccfg), arr, len(images), C.byref(h)))
+    h = _new(lib().op_sift_batch, ctx.handle, _cfg(cfg), arr, len(images))
     del keep
     return Features(ctx, h)
 
@@ -709,9 +695,7 @@ def sift_staged(ctx: Context, cfg, image, planes=True):
     """Staged single-image run -> object with the same fields as tests' ``SiftStages``."""
     L = lib()
     arr, keep = _mk_images([image])
-    ccfg = OpConfig.from_config(cfg)
-    hd = C.c_void_p()
-    check(L.op_sift_staged(ctx.handle, C.byref(ccfg), arr, C.byref(hd)))
+    hd = _new(L.op_sift_staged, ctx.handle, _cfg(cfg), arr)
 
     class Stages:
         pass
@@ -721,7 +705,7 @@ def sift_staged(ctx: Context, cfg, image, planes=True):
         h, w = C.c_int(), C.c_int()
         L.op_sift_dump_working_dims(hd, C.byref(h), C.byref(w))
         st.work = np.empty((h.value, w.value, 3), np.float32)
-        check(L.op_sift_dump_plane(ctx.handle, hd, 4, 0, 0, st.work.ctypes.data_as(C.c_void_p)))
+        check(L.op_sift_dump_plane(ctx.handle, hd, 4, 0, 0, _p(st.work)))
         st.dims = []; st.grey = {}; st.dog = {}; st.mag = {}; st.ort = {}; st.raw = {}
         for o in range(cfg.NUM_OCTAVE):
             check(L.op_sift_dump_octave_dims(hd, o, C.byref(h), C.byref(w)))
@@ -729,7 +713,7 @@ def sift_staged(ctx: Context, cfg, image, planes=True):
             if planes:
                 def grab(kind, s):
                     buf = np.empty((h.value, w.value), np.float32)
-                    check(L.op_sift_dump_plane(ctx.handle, hd, kind, o, s, buf.ctypes.data_as(C.c_void_p)))
+                    check(L.op_sift_dump_plane(ctx.handle, hd, kind, o, s, _p(buf)))
                     return buf
                 st.grey[o] = grab(5, 0)
                 for s in range(cfg.NUM_SCALE - 1):
@@ -741,18 +725,18 @@ def sift_staged(ctx: Context, cfg, image, planes=True):
                 n = L.op_sift_dump_raw_count(hd, o, s)
                 xy = np.empty((n, 2), np.int32)
                 if n:
-                    L.op_sift_dump_raw(hd, o, s, xy.ctypes.data_as(C.c_void_p))
+                    L.op_sift_dump_raw(hd, o, s, _p(xy))
                 st.raw[(o, s)] = xy
         for which, name in ((0, "refined"), (1, "oriented")):
             n = L.op_sift_dump_kp_count(hd, which)
             ints = np.empty((n, 4), np.int32); real = np.empty((n, 2), np.float64); fl = np.empty((n, 2), np.float32)
             if n:
-                L.op_sift_dump_kp(hd, which, ints.ctypes.data_as(C.c_void_p), real.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p))
+                L.op_sift_dump_kp(hd, which, _p(ints), _p(real), _p(fl))
             setattr(st, name, dict(ints=ints, real=real, fl=fl))
         k = L.op_sift_dump_kp_count(hd, 1)
         st.desc = np.empty((k, 128), np.float32); st.coor = np.empty((k, 2), np.float64)
         if k:
-            L.op_sift_dump_desc(hd, st.desc.ctypes.data_as(C.c_void_p), st.coor.ctypes.data_as(C.c_void_p))
+            L.op_sift_dump_desc(hd, _p(st.desc), _p(st.coor))
     finally:
         L.op_sift_dump_free(hd)
     del keep
@@ -763,12 +747,13 @@ def debug_math(ctx: Context, which: int, x, y=None):
     x = np.ascontiguousarray(x, np.float32)
     y = np.ascontiguousarray(y, np.float32) if y is not None else x
     out = np.empty_like(x)
-    check(lib().op_debug_math(ctx.handle, which, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.size, out.ctypes.data_as(C.c_void_p)))
+    check(lib().op_debug_math(ctx.handle, which, _p(x), _p(y), x.size, _p(out)))
     return out
 
 
-class Matches:
+class Matches(_Handle):
     """``op_matches`` handle (kept for the RANSAC stage)."""
+    _free_fn = "op_matches_free"
 
     def __init__(self, handle, npairs):
         self.handle = handle; self.npairs = npairs
@@ -779,17 +764,17 @@ class Matches:
         n = L.op_matches_count(self.handle, p)
         a = np.empty((n, 2), np.int32)
         if n:
-            check(L.op_matches_copy(self.handle, p, a.ctypes.data_as(C.c_void_p)))
+            check(L.op_matches_copy(self.handle, p, _p(a)))
         return a
 
     def lists(self):
         """every pair's (M, 2) int32 list: one library call, one D2H of the resident lists"""
         L = lib()
         offs = np.empty(self.npairs + 1, np.int64)
-        check(L.op_matches_copy_all(self.handle, None, offs.ctypes.data_as(C.c_void_p)))
+        check(L.op_matches_copy_all(self.handle, None, _p(offs)))
         flat = np.empty((int(offs[-1]), 2), np.int32)
         if len(flat):
-            check(L.op_matches_copy_all(self.handle, flat.ctypes.data_as(C.c_void_p), None))
+            check(L.op_matches_copy_all(self.handle, _p(flat), None))
         return [flat[offs[p]: offs[p + 1]] for p in range(self.npairs)]
 
     @property
@@ -800,64 +785,49 @@ class Matches:
     def from_host(cls, lists):
         lists = [np.ascontiguousarray(a, np.int32).reshape(-1, 2) for a in lists]
         n = len(lists)
-        ptrs = (C.c_void_p * n)(*[a.ctypes.data_as(C.c_void_p) for a in lists])
+        ptrs = (C.c_void_p * n)(*[_p(a) for a in lists])
         counts = (C.c_int * n)(*[len(a) for a in lists])
-        h = C.c_void_p()
-        check(lib().op_matches_from_host(ptrs, counts, n, C.byref(h)))
-        return cls(h, n)
+        return cls(_new(lib().op_matches_from_host, ptrs, counts, n), n)
 
     @classmethod
     def concat(cls, ctx, a, b):
         """a's pairs followed by b's as one handle (op_matches_concat): one op_ransac_pairs call for both"""
-        h = C.c_void_p()
-        check(lib().op_matches_concat(ctx.handle, a.handle, b.handle, C.byref(h)))
-        return cls(h, a.npairs + b.npairs)
+        return cls(_new(lib().op_matches_concat, ctx.handle, a.handle, b.handle), a.npairs + b.npairs)
 
-    def free(self):
-        if self.handle:
-            lib().op_matches_free(self.handle); self.handle = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+def _match(owner, cfg, feats, pairs) -> Matches:
+    """op_match_pairs on a Context, op_match_pairs_multi on a Group"""
+    pr = _pairs(pairs)
+    fn = lib().op_match_pairs_multi if isinstance(owner, Group) else lib().op_match_pairs
+    return Matches(_new(fn, owner.handle, _cfg(cfg), feats.handle, _p(pr), len(pr)), len(pr))
 
 
 def match_pairs_handle(ctx: Context, cfg, feats: Features, pairs) -> Matches:
-    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-    ccfg = OpConfig.from_config(cfg)
-    h = C.c_void_p()
-    check(lib().op_match_pairs(ctx.handle, C.byref(ccfg), feats.handle, pr.ctypes.data_as(C.c_void_p), len(pr), C.byref(h)))
-    return Matches(h, len(pr))
+    return _match(ctx, cfg, feats, pairs)
+
+
+def _ransac(owner, cfg, feats, matches, pairs, shapes_wh, seeds, base_seed):
+    """op_ransac_pairs on a Context, op_ransac_pairs_multi on a Group -> (result handle, the pair list as passed): the caller
+    reads the result and frees it with op_ransac_free"""
+    pr, sh, sd = _pairs(pairs), _shapes(shapes_wh), _seeds(seeds)
+    fn = lib().op_ransac_pairs_multi if isinstance(owner, Group) else lib().op_ransac_pairs
+    return _new(fn, owner.handle, _cfg(cfg), feats.handle, matches.handle, _p(pr), len(pr), _p(sh), _p(sd), int(base_seed)), pr
 
 
 def ransac_pairs(ctx: Context, cfg, feats: Features, matches: Matches, pairs, shapes_wh, seeds=None, base_seed=0):
     """Batched TransformEstimation::get_transform. shapes_wh: (n_images, 2) of (w, h).
     -> list of dict(ok, confidence, homo (3,3), inliers, best_hyp, best_count) per pair."""
     L = lib()
-    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-    sh = np.ascontiguousarray(np.asarray(shapes_wh, np.int32).reshape(-1, 2))
-    sd = np.ascontiguousarray(np.asarray(seeds, np.uint32)) if seeds is not None else None
-    ccfg = OpConfig.from_config(cfg)
-    h = C.c_void_p()
-    check(L.op_ransac_pairs(ctx.handle, C.byref(ccfg), feats.handle, matches.handle, pr.ctypes.data_as(C.c_void_p), len(pr),
-                            sh.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
-                            int(base_seed), C.byref(h)))
-    return _unpack_ransac(h, len(pr))
-
-
-def _unpack_ransac(h, npairs):
-    L = lib()
+    h, pr = _ransac(ctx, cfg, feats, matches, pairs, shapes_wh, seeds, base_seed)
     out = []
     try:
-        for p in range(npairs):
+        for p in range(len(pr)):
             homo = np.zeros(9, np.float64)
-            check(L.op_ransac_homo(h, p, homo.ctypes.data_as(C.c_void_p)))
+            check(L.op_ransac_homo(h, p, _p(homo)))
             n = L.op_ransac_inlier_count(h, p)
             inl = np.empty(n, np.int32)
             if n:
-                check(L.op_ransac_inliers(h, p, inl.ctypes.data_as(C.c_void_p)))
+                check(L.op_ransac_inliers(h, p, _p(inl)))
             bh = C.c_int(); bc = C.c_int()
             check(L.op_ransac_best(h, p, C.byref(bh), C.byref(bc)))
             out.append(dict(ok=bool(L.op_ransac_ok(h, p)), confidence=L.op_ransac_confidence(h, p), homo=homo.reshape(3, 3),
@@ -869,19 +839,13 @@ def _unpack_ransac(h, npairs):
 
 def ransac_pairs_summary(ctx: Context, cfg, feats: Features, matches: Matches, pairs, shapes_wh, base_seed=0, seeds=None):
     """op_ransac_pairs without unpacking every pair into Python: -> (accepted pairs, total inliers)."""
-    L = lib()
-    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-    sh = np.ascontiguousarray(np.asarray(shapes_wh, np.int32).reshape(-1, 2))
-    sd = np.ascontiguousarray(np.asarray(seeds, np.uint32)) if seeds is not None else None
-    ccfg = OpConfig.from_config(cfg)
-    h = C.c_void_p()
-    check(L.op_ransac_pairs(ctx.handle, C.byref(ccfg), feats.handle, matches.handle, pr.ctypes.data_as(C.c_void_p), len(pr),
-                            sh.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
-                            int(base_seed), C.byref(h)))
-    ok = C.c_int(); inl = C.c_int64()
-    check(L.op_ransac_summary(h, C.byref(ok), C.byref(inl)))
-    L.op_ransac_free(h)
-    return ok.value, inl.value
+    h, _ = _ransac(ctx, cfg, feats, matches, pairs, shapes_wh, seeds, base_seed)
+    try:
+        ok = C.c_int(); inl = C.c_int64()
+        check(lib().op_ransac_summary(h, C.byref(ok), C.byref(inl)))
+        return ok.value, inl.value
+    finally:
+        lib().op_ransac_free(h)
 
 
 def ransac_pairwise_table(ctx: Context, cfg, feats: Features, matches: Matches, pairs, shapes_wh, base_seed=0, seeds=None, table_pairs=None):
@@ -889,24 +853,15 @@ def ransac_pairwise_table(ctx: Context, cfg, feats: Features, matches: Matches, 
     without unpacking a pair into Python.  -> (ij (E, 2) int32, conf (E,) float32, homo (E, 9) float64, cnt (E,) int32,
     pts (sum cnt, 4) float64, accepted pairs): the arguments of pano_estimate_cameras; E = 2 x accepted pairs."""
     L = lib()
-    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-    sh = np.ascontiguousarray(np.asarray(shapes_wh, np.int32).reshape(-1, 2))
-    sd = np.ascontiguousarray(np.asarray(seeds, np.uint32)) if seeds is not None else None
-    ccfg = OpConfig.from_config(cfg)
-    h = C.c_void_p()
-    check(L.op_ransac_pairs(ctx.handle, C.byref(ccfg), feats.handle, matches.handle, pr.ctypes.data_as(C.c_void_p), len(pr),
-                            sh.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
-                            int(base_seed), C.byref(h)))
+    h, pr = _ransac(ctx, cfg, feats, matches, pairs, shapes_wh, seeds, base_seed)
     try:
         ne = C.c_int(); npt = C.c_int64()
         check(L.op_pairwise_table_size(h, C.byref(ne), C.byref(npt)))
         E, P = ne.value, npt.value
         ij = np.zeros((max(E, 1), 2), np.int32); conf = np.zeros(max(E, 1), np.float32); homo = np.zeros((max(E, 1), 9), np.float64)
         cnt = np.zeros(max(E, 1), np.int32); pts = np.zeros((max(P, 1), 4), np.float64)
-        tp = pr if table_pairs is None else np.ascontiguousarray(np.asarray(table_pairs, np.int32).reshape(-1, 2))   # (tests: a list other than the call's is refused)
-        check(L.op_pairwise_table(ctx.handle, feats.handle, matches.handle, h, tp.ctypes.data_as(C.c_void_p), len(tp),
-                                  ij.ctypes.data_as(C.c_void_p), conf.ctypes.data_as(C.c_void_p), homo.ctypes.data_as(C.c_void_p),
-                                  cnt.ctypes.data_as(C.c_void_p), pts.ctypes.data_as(C.c_void_p)))
+        tp = pr if table_pairs is None else _pairs(table_pairs)   # (tests: a list other than the call's is refused)
+        check(L.op_pairwise_table(ctx.handle, feats.handle, matches.handle, h, _p(tp), len(tp), _p(ij), _p(conf), _p(homo), _p(cnt), _p(pts)))
         return ij[:E], conf[:E], homo[:E], cnt[:E], pts[:P], E // 2
     finally:
         L.op_ransac_free(h)
@@ -915,20 +870,16 @@ def ransac_pairwise_table(ctx: Context, cfg, feats: Features, matches: Matches, 
 def match_pairs(ctx: Context, cfg, feats: Features, pairs):
     """All requested image pairs in one call -> list of (M, 2) int32 arrays of
     <idx in image i, idx in image j>, sorted by (first, second) (``MatchData``, matcher.hh:14-25)."""
-    L = lib()
-    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-    ccfg = OpConfig.from_config(cfg)
-    h = C.c_void_p()
-    check(L.op_match_pairs(ctx.handle, C.byref(ccfg), feats.handle, pr.ctypes.data_as(C.c_void_p), len(pr), C.byref(h)))
-    mh = Matches(h, len(pr))
+    mh = _match(ctx, cfg, feats, pairs)
     try:
         return [a.copy() for a in mh.lists()]
     finally:
         mh.free()
 
 
-class Canvas:
+class Canvas(_Handle):
     """``op_canvas``: device-resident H x W x 3 fp32 result of a blend / warp."""
+    _free_fn = "op_canvas_free"
 
     def __init__(self, ctx: Context, handle):
         self.ctx = ctx; self.handle = handle
@@ -942,7 +893,7 @@ class Canvas:
 
     def numpy(self):
         out = np.empty((self.h, self.w, 3), np.float32)
-        check(lib().op_canvas_copy(self.ctx.handle, self.handle, out.ctypes.data_as(C.c_void_p)))
+        check(lib().op_canvas_copy(self.ctx.handle, self.handle, _p(out)))
         return out
 
     @classmethod
@@ -951,18 +902,13 @@ class Canvas:
         a = np.ascontiguousarray(array, np.float32)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"Canvas.upload: expected (H, W, 3) float32, got {a.shape}")
-        h = C.c_void_p()
-        check(lib().op_canvas_upload(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], C.byref(h)))
-        return cls(ctx, h)
+        return cls(ctx, _new(lib().op_canvas_upload, ctx.handle, _p(a), a.shape[0], a.shape[1]))
 
     def perspective(self, inv, cfg) -> "Canvas":
         """CylinderStitcher::perspective_correction's LinearBlender pass (cylstitcher.cc:170-179) under cfg's ORDERED_INPUT and
         LAZY_READ: pixel (i, j) of the result samples this canvas at trans2d(j, i) of ``inv`` (op_canvas_perspective)"""
         m = np.ascontiguousarray(np.asarray(inv, np.float64).reshape(9))
-        ccfg = OpConfig.from_config(cfg)
-        h = C.c_void_p()
-        check(lib().op_canvas_perspective(self.ctx.handle, C.byref(ccfg), self.handle, m.ctypes.data_as(C.c_void_p), C.byref(h)))
-        return Canvas(self.ctx, h)
+        return Canvas(self.ctx, _new(lib().op_canvas_perspective, self.ctx.handle, _cfg(cfg), self.handle, _p(m)))
 
     def crop(self):
         """crop() of the reference (lib/imgproc.cc:200-235) -> (Canvas, (x0, y0))"""
@@ -973,41 +919,24 @@ class Canvas:
     def numpy_u8(self):
         """write_rgb quantisation on the device, bytes over PCIe"""
         out = np.empty((self.h, self.w, 3), np.uint8)
-        check(lib().op_canvas_copy_u8(self.ctx.handle, self.handle, out.ctypes.data_as(C.c_void_p)))
+        check(lib().op_canvas_copy_u8(self.ctx.handle, self.handle, _p(out)))
         return out
 
     def png_bytes(self) -> bytes:
         """the canvas as a PNG file (8-bit RGB, numpy_u8()'s pixels), encoded on the device (op_canvas_encode_png)"""
-        h = C.c_void_p()
-        check(lib().op_canvas_encode_png(self.ctx.handle, self.handle, C.byref(h)))
-        return _take_file(self.ctx, h, "op_png")
+        return _take_file(self.ctx, _new(lib().op_canvas_encode_png, self.ctx.handle, self.handle), "op_png")
 
     def write_png(self, path):
-        data = self.png_bytes()
-        with open(path, "wb") as f:
-            f.write(data)
+        _write(path, self.png_bytes())
 
     def jpeg_bytes(self, quality=90, subsampling="420") -> bytes:
         """the canvas as a baseline JPEG file (numpy_u8()'s pixels; every byte what libjpeg writes for them at this quality and
         sampling, with restart markers), encoded on the device (op_canvas_encode_jpeg)"""
-        h = C.c_void_p()
-        check(lib().op_canvas_encode_jpeg(self.ctx.handle, self.handle, int(quality), _jpeg_subsampling(subsampling), C.byref(h)))
+        h = _new(lib().op_canvas_encode_jpeg, self.ctx.handle, self.handle, int(quality), _jpeg_subsampling(subsampling))
         return _take_file(self.ctx, h, "op_jpeg")
 
     def write_jpeg(self, path, quality=90, subsampling="420"):
-        data = self.jpeg_bytes(quality, subsampling)
-        with open(path, "wb") as f:
-            f.write(data)
-
-    def free(self):
-        if self.handle:
-            lib().op_canvas_free(self.handle); self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        _write(path, self.jpeg_bytes(quality, subsampling))
 
 
 def _take_file(ctx: Context, handle, prefix) -> bytes:
@@ -1015,7 +944,7 @@ def _take_file(ctx: Context, handle, prefix) -> bytes:
     size, copy, free = (getattr(lib(), f"{prefix}_{f}") for f in ("size", "copy", "free"))
     try:
         out = np.empty(size(handle), np.uint8)
-        check(copy(ctx.handle, handle, out.ctypes.data_as(C.c_void_p)))
+        check(copy(ctx.handle, handle, _p(out)))
         return out.tobytes()
     finally:
         free(handle)
@@ -1031,9 +960,7 @@ def _rgb_u8(array, who):
 def encode_png_u8(ctx: Context, array) -> bytes:
     """PNG file of an (H, W, 3) uint8 array in host memory, through the device encoder (op_png_encode_u8)"""
     a = _rgb_u8(array, "encode_png_u8")
-    h = C.c_void_p()
-    check(lib().op_png_encode_u8(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], C.byref(h)))
-    return _take_file(ctx, h, "op_png")
+    return _take_file(ctx, _new(lib().op_png_encode_u8, ctx.handle, _p(a), a.shape[0], a.shape[1]), "op_png")
 
 
 JPEG_444, JPEG_420 = 0, 1      # OP_JPEG_444, OP_JPEG_420
@@ -1051,23 +978,18 @@ def _jpeg_subsampling(s) -> int:
 def encode_jpeg_u8(ctx: Context, array, quality=90, subsampling="420") -> bytes:
     """JPEG file of an (H, W, 3) uint8 array in host memory, through the device encoder (op_jpeg_encode_u8)"""
     a = _rgb_u8(array, "encode_jpeg_u8")
-    h = C.c_void_p()
-    check(lib().op_jpeg_encode_u8(ctx.handle, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], int(quality),
-                                  _jpeg_subsampling(subsampling), C.byref(h)))
+    h = _new(lib().op_jpeg_encode_u8, ctx.handle, _p(a), a.shape[0], a.shape[1], int(quality), _jpeg_subsampling(subsampling))
     return _take_file(ctx, h, "op_jpeg")
 
 
 def blend_prepare(cfg, shapes_wh, homos, proj_method, identity_idx):
     """Host geometry of ``ConnectedImages`` (calc_inverse_homo, update_proj_range,
     get_final_resolution: stitcher_image.cc:36-114) -> (OpBlendGeom, homo_inv (n,9), ranges (n,4))."""
-    sh = np.ascontiguousarray(np.asarray(shapes_wh, np.int32).reshape(-1, 2))
+    sh = _shapes(shapes_wh)
     n = len(sh)
     homo = np.ascontiguousarray(np.asarray(homos, np.float64).reshape(n, 9))
-    ccfg = OpConfig.from_config(cfg)
     g = OpBlendGeom(); hinv = np.zeros((n, 9), np.float64); ranges = np.zeros((n, 4), np.float64)
-    check(lib().op_blend_prepare(C.byref(ccfg), int(proj_method), int(identity_idx), n, sh.ctypes.data_as(C.c_void_p),
-                                 homo.ctypes.data_as(C.c_void_p), C.byref(g), hinv.ctypes.data_as(C.c_void_p),
-                                 ranges.ctypes.data_as(C.c_void_p)))
+    check(lib().op_blend_prepare(_cfg(cfg), int(proj_method), int(identity_idx), n, _p(sh), _p(homo), C.byref(g), _p(hinv), _p(ranges)))
     return g, hinv, ranges
 
 
@@ -1125,43 +1047,43 @@ class BlendCall:
                 raise ValueError(f"vignette must hold the 3 coefficients a1, a2, a3, got {self.vignette.shape}")
             if self.gains is not None and self.gains.ndim != 2:
                 raise ValueError("vignetting takes per-image gains (n, 3), not block gains")
+        self._gains_p, self._vignette_p = _p(self.gains), _p(self.vignette)      # of the arrays this object keeps
         self._fn = lib().op_blend
 
     def __call__(self) -> Canvas:
         h = C.c_void_p()
         if self.vignette is not None:
             check(lib().op_blend_vignette(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n,
-                                          None if self.gains is None else self.gains.ctypes.data_as(C.c_void_p),
-                                          self.vignette.ctypes.data_as(C.c_void_p), C.byref(h)))
+                                          self._gains_p, self._vignette_p, C.byref(h)))
         elif self.gains is None:
             check(self._fn(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, C.byref(h)))
         elif self.gains.ndim == 4:
             by, bx = self.gains.shape[1:3]
             check(lib().op_blend_block_gains(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(bx), int(by),
-                                             self.gains.ctypes.data_as(C.c_void_p), C.byref(h)))
+                                             self._gains_p, C.byref(h)))
         else:
-            check(lib().op_blend_gains(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n,
-                                       self.gains.ctypes.data_as(C.c_void_p), C.byref(h)))
+            check(lib().op_blend_gains(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, self._gains_p, C.byref(h)))
         return Canvas(self.ctx, h)
+
+    def _overlap(self, fn, args, per_pair):
+        """one of the three overlap passes over this call's canvas -> (count, sums): per pair, sums of shape ``per_pair`` and
+        one count for each of their last axes"""
+        npairs = self.n * (self.n - 1) // 2
+        rows = max(npairs, 1)
+        count = np.zeros((rows,) + per_pair[:-1], np.int64); sums = np.zeros((rows,) + per_pair, np.int64)
+        check(fn(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, *args, _p(count), _p(sums)))
+        return count[:npairs], sums[:npairs]
 
     def overlap_sums(self, stride=1):
         """op_gain_overlap over this call's canvas -> (count (P,) int64, sums (P, 6) int64: S_ab[3], S_ba[3] in units of
         2^-32), P = n (n - 1) / 2, pair (a < b) at index pair_index(n, a, b)."""
-        npairs = self.n * (self.n - 1) // 2
-        count = np.zeros(max(npairs, 1), np.int64); sums = np.zeros((max(npairs, 1), 6), np.int64)
-        check(lib().op_gain_overlap(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(stride),
-                                    count.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
-        return count[:npairs], sums[:npairs]
+        return self._overlap(lib().op_gain_overlap, (int(stride),), (6,))
 
     def vignette_overlap_sums(self, stride=VIG_STRIDE, clip=VIG_CLIP):
         """op_vignette_overlap over this call's canvas -> (count (P,) int64, moments (P, 30) int64 in units of 2^-32):
         A_k = sum Ya^2 rho_b^k at [p, k], B_k = sum Yb^2 rho_a^k at [p, 7 + k] (k = 0..6), C_ij = sum Ya Yb rho_a^i rho_b^j
         at [p, 14 + 4 i + j] (i, j = 0..3); samples whose largest channel exceeds clip are left out."""
-        npairs = self.n * (self.n - 1) // 2
-        count = np.zeros(max(npairs, 1), np.int64); mom = np.zeros((max(npairs, 1), VIG_MOMENTS), np.int64)
-        check(lib().op_vignette_overlap(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(stride),
-                                        float(clip), count.ctypes.data_as(C.c_void_p), mom.ctypes.data_as(C.c_void_p)))
-        return count[:npairs], mom[:npairs]
+        return self._overlap(lib().op_vignette_overlap, (int(stride), float(clip)), (VIG_MOMENTS,))
 
     def block_overlap_sums(self, bx, by, stride=1):
         """op_gain_block_overlap -> (count (P, B, B) int64, sums (P, B, B, 6) int64 fixed point), B = bx * by: the entry
@@ -1170,11 +1092,7 @@ class BlendCall:
         npairs, B = self.n * (self.n - 1) // 2, int(bx) * int(by)
         if npairs * B * B > GAIN_BLOCK_MAX_ENTRIES:       # refused by the library; do not allocate the arrays first
             raise OpenPanoHipError(f"op_gain_block_overlap: {npairs * B * B} unit-pair entries exceed {GAIN_BLOCK_MAX_ENTRIES}")
-        rows = max(npairs, 1)
-        count = np.zeros((rows, B, B), np.int64); sums = np.zeros((rows, B, B, 6), np.int64)
-        check(lib().op_gain_block_overlap(self.ctx.handle, C.byref(self.ccfg), C.byref(self.geom), self.arr, self.n, int(stride),
-                                          int(bx), int(by), count.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
-        return count[:npairs], sums[:npairs]
+        return self._overlap(lib().op_gain_block_overlap, (int(stride), int(bx), int(by)), (B, B, 6))
 
 
 def blend(ctx: Context, cfg, images, homos, proj_method, identity_idx, gains=None, vignette=None) -> Canvas:
@@ -1213,8 +1131,8 @@ def gain_solve(n, count, sums, sigma_n=GAIN_SIGMA_N, sigma_g=GAIN_SIGMA_G, per_c
     if len(c) != npairs or len(s) != npairs:
         raise ValueError(f"{n} images need {npairs} pairs, got {len(c)} counts and {len(s)} sums")
     out = np.zeros((n, 3), np.float32)
-    check(lib().op_gain_solve(int(n), c.ctypes.data_as(C.c_void_p) if npairs else None, s.ctypes.data_as(C.c_void_p) if npairs else None,
-                              float(sigma_n), float(sigma_g), int(bool(per_channel)), out.ctypes.data_as(C.c_void_p)))
+    check(lib().op_gain_solve(int(n), _p(c if npairs else None), _p(s if npairs else None), float(sigma_n), float(sigma_g),
+                              int(bool(per_channel)), _p(out)))
     return out
 
 
@@ -1233,9 +1151,8 @@ def gain_block_solve(n, bx, by, count, sums, sigma_n=GAIN_SIGMA_N, sigma_g=GAIN_
     if len(c) != npairs * B * B or len(s) != 6 * npairs * B * B:
         raise ValueError(f"{n} images at {bx} x {by} need {npairs * B * B} entries, got {len(c)} counts and {len(s) // 6} sums")
     out = np.zeros((n, int(by), int(bx), 3), np.float32)
-    check(lib().op_gain_block_solve(int(n), int(bx), int(by), c.ctypes.data_as(C.c_void_p) if npairs else None,
-                                    s.ctypes.data_as(C.c_void_p) if npairs else None, float(sigma_n), float(sigma_g), float(sigma_s),
-                                    int(bool(per_channel)), out.ctypes.data_as(C.c_void_p)))
+    check(lib().op_gain_block_solve(int(n), int(bx), int(by), _p(c if npairs else None), _p(s if npairs else None), float(sigma_n),
+                                    float(sigma_g), float(sigma_s), int(bool(per_channel)), _p(out)))
     return out
 
 
@@ -1257,9 +1174,8 @@ def vignette_solve(n, count, moments, degree=3, sigma_n=VIG_SIGMA_N, sigma_g=VIG
     if len(c) != npairs or len(m) != npairs:
         raise ValueError(f"{n} images need {npairs} pairs, got {len(c)} counts and {len(m)} moment rows")
     gains = np.zeros((n, 3), np.float32); poly = np.zeros(3, np.float32)
-    check(lib().op_vignette_solve(int(n), c.ctypes.data_as(C.c_void_p) if npairs else None, m.ctypes.data_as(C.c_void_p) if npairs else None,
-                                  int(degree), float(sigma_n), float(sigma_g), float(sigma_v), gains.ctypes.data_as(C.c_void_p),
-                                  poly.ctypes.data_as(C.c_void_p)))
+    check(lib().op_vignette_solve(int(n), _p(c if npairs else None), _p(m if npairs else None), int(degree), float(sigma_n),
+                                  float(sigma_g), float(sigma_v), _p(gains), _p(poly)))
     return gains, poly
 
 
@@ -1283,28 +1199,24 @@ def perspective_homography(proj_min, ref_wh, first_wh, first_homo, last_wh, last
     fh = np.ascontiguousarray(np.asarray(first_homo, np.float64).reshape(9))
     lh = np.ascontiguousarray(np.asarray(last_homo, np.float64).reshape(9))
     inv = np.zeros(9); corners = np.zeros(8)
-    check(lib().op_perspective_homography(C.byref(g), int(ref_wh[0]), int(ref_wh[1]), int(first_wh[0]), int(first_wh[1]),
-                                          fh.ctypes.data_as(C.c_void_p), int(last_wh[0]), int(last_wh[1]), lh.ctypes.data_as(C.c_void_p),
-                                          int(canvas_wh[0]), int(canvas_wh[1]), inv.ctypes.data_as(C.c_void_p),
-                                          corners.ctypes.data_as(C.c_void_p)))
+    check(lib().op_perspective_homography(C.byref(g), int(ref_wh[0]), int(ref_wh[1]), int(first_wh[0]), int(first_wh[1]), _p(fh),
+                                          int(last_wh[0]), int(last_wh[1]), _p(lh), int(canvas_wh[0]), int(canvas_wh[1]),
+                                          _p(inv), _p(corners)))
     return inv.reshape(3, 3), corners.reshape(4, 2)
 
 
 def cyl_warp_shape(cfg, w, h, h_factor, pts=None):
     """Host part of ``CylinderWarper::warp`` -> (new_w, new_h, offset (2,), warped centred pts)."""
-    ccfg = OpConfig.from_config(cfg)
     p = np.ascontiguousarray(pts, np.float64).reshape(-1, 2).copy() if pts is not None else np.zeros((0, 2))
     nw, nh = C.c_int(), C.c_int(); off = np.zeros(2)
-    check(lib().op_cyl_warp_shape(C.byref(ccfg), int(w), int(h), float(h_factor), p.ctypes.data_as(C.c_void_p) if len(p) else None,
-                                  len(p), C.byref(nw), C.byref(nh), off.ctypes.data_as(C.c_void_p)))
+    check(lib().op_cyl_warp_shape(_cfg(cfg), int(w), int(h), float(h_factor), _p(p if len(p) else None), len(p),
+                                  C.byref(nw), C.byref(nh), _p(off)))
     return nw.value, nh.value, off, p
 
 
 def cyl_warp(ctx: Context, cfg, image, h_factor) -> Canvas:
     """``CylinderWarper::warp``'s pixels; image: float32, or uint8 decoder bytes (host array or device tuple)"""
     arr, keep = _mk_images([image])
-    ccfg = OpConfig.from_config(cfg)
-    h = C.c_void_p()
-    check(lib().op_cyl_warp(ctx.handle, C.byref(ccfg), arr, float(h_factor), C.byref(h)))
+    h = _new(lib().op_cyl_warp, ctx.handle, _cfg(cfg), arr, float(h_factor))
     del keep
     return Canvas(ctx, h)

@@ -31,8 +31,7 @@ def main():
     torch.cuda.set_stream(stream)
     for name in ["product"] + list(a.libs):
         path = os.path.join(ROOT, "openpano_amd", "libopenpano_hip.so") if name == "product" else os.path.abspath(name)
-        hip._lib = None
-        hip.LIB_PATH = path
+        hip.use_library(path)
         ctx = hip.Context(0, stream.cuda_stream)
         res = bench.run_blend(hip, ctx, PanoConfig(), inputs, H, W, a, lambda m: None)
         homos = res.pop("_homos")

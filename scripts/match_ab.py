@@ -41,8 +41,7 @@ def main():
     product = hip.LIB_PATH                       # openpano_amd/libopenpano_hip.so, or OPENPANO_HIP_LIB (one build per process: profilers)
     for name in ["product"] + list(a.libs):
         path = product if name == "product" else os.path.abspath(name)
-        hip._lib = None
-        hip.LIB_PATH = path
+        hip.use_library(path)
         ctx = hip.Context(0, stream.cuda_stream)
         short = os.path.basename(path).replace("libopenpano_hip_", "").replace(".so", "")
         for jname, inputs in jobs:

@@ -24,7 +24,7 @@ def main():
     product = hip.LIB_PATH
     for name in ["product"] + list(a.libs):
         path = product if name == "product" else os.path.abspath(name)
-        hip._lib = None; hip.LIB_PATH = path
+        hip.use_library(path)
         ctx = hip.Context(0)
         f = hip.sift_batch(ctx, cfg, views)
         allp = [(i, j) for i in range(38) for j in range(i + 1, 38)]

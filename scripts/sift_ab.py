@@ -49,8 +49,7 @@ def main():
     out = {}
     for name in libs:
         path = os.path.join(ROOT, "openpano_amd", "libopenpano_hip.so") if name == "product" else os.path.abspath(name)
-        hip._lib = None
-        hip.LIB_PATH = path
+        hip.use_library(path)
         ctx = hip.Context(0, stream.cuda_stream)
         call = hip.SiftCall(ctx, cfg, inputs)
         f = None

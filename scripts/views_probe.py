@@ -13,9 +13,6 @@ stream before it returns) and the kernel time of the context's HIP-event profile
 `kernel_ms` is the kernel that reads the sources ("blend linear" / "multiband first level"); `all_kernels_ms` every
 bracketed device stage of the call.  The canvases of the four legs are compared (they must be equal).
 
-With OPENPANO_HIP_LIB pointing at a library built before byte views existed, only the fp32 legs run: resident_f32's
-kernel time there is the figure the new library is held against.
-
     python scripts/views_probe.py [--steps 10] [--out profiles/views_probe_latest.json] [--scene-cache /tmp/scene.npz]"""
 import argparse
 import hashlib
@@ -58,14 +55,9 @@ def main():
     stream = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(stream)
     ctx = hip.Context(0, stream.cuda_stream)
-    has_u8 = hasattr(hip.lib(), "op_views_upload")
     d_f = [torch.from_numpy(v).to(dev) for v in f]
-    legs = {"host_f32": f, "resident_f32": [(t.data_ptr(), H, W) for t in d_f]}
-    resident = None
-    if has_u8:
-        resident = hip.Views.upload(ctx, np.stack(b))
-        legs["host_u8"] = b
-        legs["resident_u8"] = resident
+    resident = hip.Views.upload(ctx, np.stack(b))
+    legs = {"host_f32": f, "resident_f32": [(t.data_ptr(), H, W) for t in d_f], "host_u8": b, "resident_u8": resident}
     torch.cuda.synchronize()
 
     def stat(xs):
@@ -89,7 +81,7 @@ def main():
         return {"wall_ms": stat(wall), "kernel_ms": stat(kern), "all_kernels_ms": stat(allk)}
 
     out = {"_meta": {"lib_sha256_16": hashlib.sha256(open(hip.LIB_PATH, "rb").read()).hexdigest()[:16],
-                     "device": torch.cuda.get_device_name(0), "steps": a.steps, "byte_views": has_u8,
+                     "device": torch.cuda.get_device_name(0), "steps": a.steps,
                      "workload": f"synth.pano_scene({n}, {H}, {W}, seed=38, proj='camera'), spherical",
                      "view_bytes": {"f32": 12 * H * W * n, "u8": 3 * H * W * n}}}
     for key, mb in (("linear", 0), ("multiband5", 5)):
@@ -106,8 +98,7 @@ def main():
             if ref is None:
                 ref = got
             out[key][leg]["equals_host_f32"] = bool(np.array_equal(got, ref))
-    if resident is not None:
-        resident.free()
+    resident.free()
     ctx.close()
     print(json.dumps(out))
     if a.out:
