@@ -623,6 +623,50 @@ int op_jpeg_exif(const unsigned char* file, int64_t size, int* orientation, int*
 int op_views_decode_jpeg_oriented(op_ctx* ctx, const unsigned char* const* files, const int64_t* sizes, int n,
                                   const int* orientation, op_views** out);
 
+/* ---- RE-PROJECTION OF A FINISHED PANORAMA (additive within ABI 12) -- replaces planet(fname) (main.cc:294-331), the one
+ * thing the reference's CLI does with a finished panorama, and adds what it has no way to make: a rectilinear view in a chosen
+ * direction and the six faces of a cube.  Each is a pure gather from an equirectangular canvas, one thread per output pixel;
+ * the canvas stays on the device and the result is a canvas like any other (crop, PNG and JPEG output take it).  DESIGN.md
+ * section 19 gives the maps; tests/reproject_cases.py restates them in numpy, and the device equals that restatement bit for
+ * bit: the per-pixel angle is pano_atan2 (csrc/pano_angle.hpp: + - * / only, within 4e-15 rad of atan2), the square root is
+ * correctly rounded on both sides, the colour arithmetic is interpolate's fp32 sequence (lib/imgproc.cc:135-156).
+ *
+ * op_pano_frame: where the canvas sits on the sphere.  Column c is longitude lon0 + c * step_lon, row r is latitude
+ * lat0 + r * step_lat, y down as spherical::homo2proj gives them (projection.hh:50-52).  wrap = 1 is the caller's statement
+ * that the W columns span exactly one turn (what planet assumes): step_lon is then ignored, a longitude d past lon0, brought
+ * into [0, 2 pi), lies at column d / (M_PI * 2) * W, and the taps right of the last column read column 0.  lon0 must then
+ * lie in [-pi, pi].  wrap is never guessed by the library.
+ * op_view_spec: what to make.  OP_VIEW_PLANET: the reference's loop operation by operation on an out_h = out_w = OUTSIZE
+ * square (main.cc:297-329; with wrap = 0 including its one-column seam of Color::NO where theta reaches w - 1); rot and focal
+ * are not read, and of the frame only wrap.  OP_VIEW_RECTILINEAR: a pinhole camera.  Output pixel (i, j) looks along
+ * d = rot * (j - (out_w - 1) / 2, i - (out_h - 1) / 2, focal), rot row-major, in the canvas's frame: x right, y down,
+ * z forward (longitude 0, latitude 0); lon = atan2(d.x, d.z), lat = atan2(d.y, hypot(d.x, d.z)).  A pixel that looks outside
+ * the canvas, or whose four taps touch Color::NO, is Color::NO.
+ * op_pano_frame_of (HOST ONLY): the frame of the canvas a spherical blend made from geometry g, or of its crop at
+ * (x0, y0): lon0 = proj_min[0] + x0 * resolution[0], lat0 likewise, the steps are the resolutions, wrap = 0.  Other
+ * projections: OP_ERR_UNSUPPORTED.
+ * op_view_look (HOST ONLY, host libm): rot = R_yaw (about y) * R_pitch (about x) * R_roll (about z), angles in radians, with
+ *   R_yaw = [c 0 s; 0 1 0; -s 0 c],  R_pitch = [1 0 0; 0 c -s; 0 s c],  R_roll = [c -s 0; s c 0; 0 0 1]:
+ * the optical axis is (sin yaw cos pitch, -sin pitch, cos yaw cos pitch), so positive yaw looks right and positive pitch looks
+ * up (towards -y).  focal = 0.5 * out_w / tan(0.5 * hfov).  Non-finite angles, hfov outside (0, pi) and sizes below 1:
+ * OP_ERR_INVALID.
+ * op_view_cube_face (HOST ONLY): face 0..5 = +x, -x, +y, -y, +z, -z as an n x n rectilinear view with focal = 0.5 * n and a
+ * signed permutation matrix (entries exactly 0, 1, -1).  The side faces +x, -x, +z, -z have -y (the zenith) at the top of the
+ * picture; +y (looking down) has +z at the top, -y (looking up) has -z at the top: the faces of an unfolded cross around +z.
+ * op_view_planet (HOST ONLY): the planet of n x n pixels (rot = identity, focal = 1, neither read).
+ * op_canvas_reproject: the view `s` of canvas `c` lying at `f`, as a new out_h x out_w canvas.  NULLs, an unknown mode, a size
+ * below 1, a planet that is not square, a non-finite field of f or s, focal <= 0, step_lat = 0, step_lon = 0 without wrap,
+ * a wrap other than 0 or 1, or wrap with lon0 outside [-pi, pi] return OP_ERR_INVALID before any device work, with nothing
+ * allocated.  An empty source gives a canvas of Color::NO.  Threading and ownership as op_blend: one call at a time per context; the caller frees the canvas. */
+typedef struct op_pano_frame { double lon0, lat0, step_lon, step_lat; int wrap; } op_pano_frame;
+typedef struct op_view_spec { int mode, out_h, out_w; double rot[9], focal; } op_view_spec;
+enum { OP_VIEW_PLANET = 0, OP_VIEW_RECTILINEAR = 1 };
+int op_pano_frame_of(const op_blend_geom* g, int x0, int y0, op_pano_frame* f);
+int op_view_look(double yaw, double pitch, double roll, double hfov, int out_w, int out_h, op_view_spec* s);
+int op_view_cube_face(int face, int n, op_view_spec* s);
+int op_view_planet(int n, op_view_spec* s);
+int op_canvas_reproject(op_ctx* ctx, const op_canvas* c, const op_pano_frame* f, const op_view_spec* s, op_canvas** out);
+
 #ifdef __cplusplus
 }
 #endif

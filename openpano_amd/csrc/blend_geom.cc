@@ -1,8 +1,9 @@
 // blend_geom.cc -- the O(n) geometry of the blend stage, on the host in fp64 with the host libm exactly like the reference:
 // calc_inverse_homo / update_proj_range / get_final_resolution (stitcher_image.cc:36-114), the bounds of
 // CylinderProject::project(Shape2D&) (warp.cc:46-67), the multiband blur's taps and the corners and homography of
-// CylinderStitcher::perspective_correction (cylstitcher.cc:140-168).  Plain C++ (no HIP), built without contraction;
-// tests/harness/photometric_solve_harness.cc and perspective_harness.cc run it under the sanitizers.
+// CylinderStitcher::perspective_correction (cylstitcher.cc:140-168); and the host parts of the re-projection (the frame of a
+// spherical canvas, the view specs, op_canvas_reproject's refusals).  Plain C++ (no HIP), built without contraction;
+// tests/harness/photometric_solve_harness.cc, perspective_harness.cc and reproject_harness.cc run it under the sanitizers.
 #include "blend_shared.hpp"
 #include "ransac_math.hpp"
 #include <algorithm>
@@ -244,4 +245,69 @@ int op_perspective_homography(const op_blend_geom* g, int ref_w, int ref_h, int 
 	return OP_OK;
 }
 
+// ---- the host parts of the re-projection (reproject.hip): where a spherical canvas sits, and the view specs ----
+int op_pano_frame_of(const op_blend_geom* g, int x0, int y0, op_pano_frame* f) {
+	if (!g || !f) OP_FAIL(OP_ERR_INVALID, "op_pano_frame_of: bad argument");
+	if (g->proj_method != 2) OP_FAIL(OP_ERR_UNSUPPORTED, "op_pano_frame_of: the canvas is not spherical");
+	f->lon0 = g->proj_min[0] + (double)x0 * g->resolution[0];
+	f->lat0 = g->proj_min[1] + (double)y0 * g->resolution[1];
+	f->step_lon = g->resolution[0]; f->step_lat = g->resolution[1];
+	f->wrap = 0;
+	return OP_OK;
+}
+
+int op_view_look(double yaw, double pitch, double roll, double hfov, int out_w, int out_h, op_view_spec* s) {
+	if (!s) OP_FAIL(OP_ERR_INVALID, "op_view_look: bad argument");
+	if (!std::isfinite(yaw) || !std::isfinite(pitch) || !std::isfinite(roll)) OP_FAIL(OP_ERR_INVALID, "op_view_look: an angle is not finite");
+	if (!(hfov > 0 && hfov < M_PI)) OP_FAIL(OP_ERR_INVALID, "op_view_look: hfov outside (0, pi)");
+	if (out_w < 1 || out_h < 1) OP_FAIL(OP_ERR_INVALID, "op_view_look: a size below 1");
+	const double cy = std::cos(yaw), sy = std::sin(yaw), cp = std::cos(pitch), sp = std::sin(pitch), cr = std::cos(roll), sr = std::sin(roll);
+	const double Ry[9] = {cy, 0, sy, 0, 1, 0, -sy, 0, cy}, Rx[9] = {1, 0, 0, 0, cp, -sp, 0, sp, cp}, Rz[9] = {cr, -sr, 0, sr, cr, 0, 0, 0, 1};
+	double A[9];
+	for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i * 3 + j] = Ry[i * 3] * Rx[j] + Ry[i * 3 + 1] * Rx[3 + j] + Ry[i * 3 + 2] * Rx[6 + j];
+	for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) s->rot[i * 3 + j] = A[i * 3] * Rz[j] + A[i * 3 + 1] * Rz[3 + j] + A[i * 3 + 2] * Rz[6 + j];
+	s->mode = OP_VIEW_RECTILINEAR; s->out_h = out_h; s->out_w = out_w;
+	s->focal = 0.5 * (double)out_w / std::tan(0.5 * hfov);
+	return OP_OK;
+}
+
+int op_view_cube_face(int face, int n, op_view_spec* s) {
+	if (!s || face < 0 || face > 5 || n < 1) OP_FAIL(OP_ERR_INVALID, "op_view_cube_face: bad argument");
+	// columns: where the picture's right, down and forward point (include/openpano_hip.h names each face's top)
+	static const double R[6][9] = {
+		{0, 0, 1, 0, 1, 0, -1, 0, 0},      // +x: right -z, down +y
+		{0, 0, -1, 0, 1, 0, 1, 0, 0},      // -x: right +z, down +y
+		{1, 0, 0, 0, 0, 1, 0, -1, 0},      // +y: right +x, down -z
+		{1, 0, 0, 0, 0, -1, 0, 1, 0},      // -y: right +x, down +z
+		{1, 0, 0, 0, 1, 0, 0, 0, 1},       // +z: right +x, down +y
+		{-1, 0, 0, 0, 1, 0, 0, 0, -1}};    // -z: right -x, down +y
+	memcpy(s->rot, R[face], sizeof(s->rot));
+	s->mode = OP_VIEW_RECTILINEAR; s->out_h = n; s->out_w = n; s->focal = 0.5 * (double)n;
+	return OP_OK;
+}
+
+int op_view_planet(int n, op_view_spec* s) {
+	if (!s || n < 1) OP_FAIL(OP_ERR_INVALID, "op_view_planet: bad argument");
+	static const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+	memcpy(s->rot, I, sizeof(s->rot));
+	s->mode = OP_VIEW_PLANET; s->out_h = n; s->out_w = n; s->focal = 1.0;
+	return OP_OK;
+}
+
 }	// extern "C"
+
+// op_canvas_reproject's refusals, here so that the sanitizer program reaches them without a device
+int reproject_check(const op_pano_frame* f, const op_view_spec* s) {
+	if (!f || !s) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: bad argument");
+	if (s->mode != OP_VIEW_PLANET && s->mode != OP_VIEW_RECTILINEAR) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: unknown mode " + std::to_string(s->mode));
+	if (s->out_h < 1 || s->out_w < 1) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: a size below 1");
+	if (s->mode == OP_VIEW_PLANET && s->out_h != s->out_w) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: a planet is square");
+	bool finite = std::isfinite(f->lon0) && std::isfinite(f->lat0) && std::isfinite(f->step_lon) && std::isfinite(f->step_lat) && std::isfinite(s->focal);
+	for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(s->rot[k]);
+	if (!finite) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: a field is not finite");
+	if (!(s->focal > 0)) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: focal is not positive");
+	if (f->wrap != 0 && f->wrap != 1) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: wrap is neither 0 nor 1");
+	if (f->step_lat == 0 || (!f->wrap && f->step_lon == 0)) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: a step is zero");
+	if (f->wrap && !(f->lon0 >= -M_PI && f->lon0 <= M_PI)) OP_FAIL(OP_ERR_INVALID, "op_canvas_reproject: wrap with lon0 outside [-pi, pi]");
+	return OP_OK;
+}

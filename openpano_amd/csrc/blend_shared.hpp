@@ -27,6 +27,7 @@ struct CylProj { double cx, cy; int r, sizefactor; };
 void roi_of(const op_blend_geom* g, const double* range, int roi[4]);
 int gauss_taps(float sigma, int window_factor, BlurTaps& t);
 CylProj cyl_projector(int w, int h, double h_factor, float focal_length);
+int reproject_check(const op_pano_frame* f, const op_view_spec* s);      // op_canvas_reproject's refusals (OP_OK or OP_ERR_INVALID)
 // photometric_solve.cc
 bool vignette_curve_positive(const double a[3]);
 int check_lens_frame(const char* who, const op_blend_image* imgs, int n);

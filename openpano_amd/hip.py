@@ -63,12 +63,27 @@ class OpBlendGeom(C.Structure):
                 ("resolution", C.c_double * 2)]
 
 
+class OpPanoFrame(C.Structure):
+    """``op_pano_frame``: where an equirectangular canvas sits on the sphere (column c at longitude lon0 + c * step_lon, row r at
+    latitude lat0 + r * step_lat; wrap = 1: the columns span exactly one turn)"""
+    _fields_ = [("lon0", C.c_double), ("lat0", C.c_double), ("step_lon", C.c_double), ("step_lat", C.c_double), ("wrap", C.c_int)]
+
+
+class OpViewSpec(C.Structure):
+    """``op_view_spec``: what ``Canvas.reproject`` makes (mode: VIEW_PLANET or VIEW_RECTILINEAR)"""
+    _fields_ = [("mode", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int), ("rot", C.c_double * 9), ("focal", C.c_double)]
+
+
+VIEW_PLANET, VIEW_RECTILINEAR = 0, 1      # OP_VIEW_PLANET, OP_VIEW_RECTILINEAR
+
+
 # The prototypes of include/openpano_hip.h, in the header's order: name -> (restype, argtypes).  lib() binds exactly these and
 # refuses a library that lacks one; tests/test_binding_header_cpu.py holds the table against the header.  Handles and array
 # arguments are c_void_p (see _p), out-parameters for scalars and the structs are typed pointers.
 _V, _S, _I, _I64, _U32, _F, _D = C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_double
 _PV, _PS, _PI, _PI64 = C.POINTER(_V), C.POINTER(_S), C.POINTER(_I), C.POINTER(_I64)
 _CFG, _IMG, _BIMG, _GEOM = C.POINTER(OpConfig), C.POINTER(OpImage), C.POINTER(OpBlendImage), C.POINTER(OpBlendGeom)
+_FRAME, _SPEC = C.POINTER(OpPanoFrame), C.POINTER(OpViewSpec)
 _BLEND = [_V, _CFG, _GEOM, _BIMG, _I]        # ctx, cfg, geometry, images, n: how every blend and overlap call starts
 _RANSAC = [_V, _CFG, _V, _V, _V, _I, _V, _V, _U32, _PV]
 
@@ -202,6 +217,12 @@ PROTOTYPES = {
     # EXIF orientation
     "op_jpeg_exif": (_I, [_S, _I64, _PI, _PI]),
     "op_views_decode_jpeg_oriented": (_I, [_V, _PS, _PI64, _I, _PI, _PV]),
+    # re-projection of a finished panorama
+    "op_pano_frame_of": (_I, [_GEOM, _I, _I, _FRAME]),
+    "op_view_look": (_I, [_D, _D, _D, _D, _I, _I, _SPEC]),
+    "op_view_cube_face": (_I, [_I, _I, _SPEC]),
+    "op_view_planet": (_I, [_I, _SPEC]),
+    "op_canvas_reproject": (_I, [_V, _V, _FRAME, _SPEC, _PV]),
 }
 
 _lib = None
@@ -910,6 +931,12 @@ class Canvas(_Handle):
         m = np.ascontiguousarray(np.asarray(inv, np.float64).reshape(9))
         return Canvas(self.ctx, _new(lib().op_canvas_perspective, self.ctx.handle, _cfg(cfg), self.handle, _p(m)))
 
+    def reproject(self, frame: OpPanoFrame, spec: OpViewSpec) -> "Canvas":
+        """this equirectangular canvas, lying at ``frame`` (pano_frame, or an OpPanoFrame of the caller's), looked at as ``spec``
+        says (view_look, view_cube_face, view_planet) -> a new canvas of spec.out_h x spec.out_w, Color::NO where nothing is
+        sampled (op_canvas_reproject)"""
+        return Canvas(self.ctx, _new(lib().op_canvas_reproject, self.ctx.handle, self.handle, C.byref(frame), C.byref(spec)))
+
     def crop(self):
         """crop() of the reference (lib/imgproc.cc:200-235) -> (Canvas, (x0, y0))"""
         h = C.c_void_p(); x0, y0 = C.c_int(), C.c_int()
@@ -1185,6 +1212,36 @@ def vignette_compensate(ctx: Context, cfg, images, homos, proj_method, identity_
     call = BlendCall(ctx, cfg, images, homos, proj_method, identity_idx)
     count, moments = call.vignette_overlap_sums(stride, clip)
     return vignette_solve(len(images), count, moments, degree, sigma_n, sigma_g, sigma_v)
+
+
+def pano_frame(geom: OpBlendGeom, x0=0, y0=0, wrap=False) -> OpPanoFrame:
+    """the frame of the canvas a spherical blend made from ``geom`` (BlendCall.geom), or of its crop at (x0, y0)
+    (op_pano_frame_of, host only).  wrap is the caller's statement that the columns span exactly one turn: never guessed."""
+    f = OpPanoFrame()
+    check(lib().op_pano_frame_of(C.byref(geom), int(x0), int(y0), C.byref(f)))
+    f.wrap = int(bool(wrap))
+    return f
+
+
+def view_look(yaw, pitch, roll, hfov, out_w, out_h) -> OpViewSpec:
+    """a pinhole view: angles in radians, positive yaw looks right, positive pitch looks up; hfov in (0, pi) (op_view_look)"""
+    s = OpViewSpec()
+    check(lib().op_view_look(float(yaw), float(pitch), float(roll), float(hfov), int(out_w), int(out_h), C.byref(s)))
+    return s
+
+
+def view_cube_face(face, n) -> OpViewSpec:
+    """cube face 0..5 = +x, -x, +y, -y, +z, -z as an n x n view (op_view_cube_face)"""
+    s = OpViewSpec()
+    check(lib().op_view_cube_face(int(face), int(n), C.byref(s)))
+    return s
+
+
+def view_planet(n) -> OpViewSpec:
+    """the reference's "little planet" of n x n pixels (op_view_planet)"""
+    s = OpViewSpec()
+    check(lib().op_view_planet(int(n), C.byref(s)))
+    return s
 
 
 def perspective_homography(proj_min, ref_wh, first_wh, first_homo, last_wh, last_homo, canvas_wh):

@@ -867,8 +867,9 @@ inline std::vector<float> hip_vignette_compensate(const Bundle& b, std::array<fl
 
 // gains: empty = op_blend; bx = by = 0: n x 3 exposure gains (op_blend_gains); bx, by >= 1: n x by x bx x 3 block gains
 // (op_blend_block_gains)
+// the blend as the device canvas the caller owns (op_canvas_free): for the crop, the encoders and hip_reproject in place
 template <typename Bundle>
-inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains, int bx, int by, const float* poly = nullptr) {
+inline op_canvas* hip_blend_canvas(const Bundle& b, const std::vector<float>& gains, int bx, int by, const float* poly = nullptr) {
 	op_ctx* ctx = HipContext::get();
 	const op_config cfg = hip_config_snapshot();
 	const int n = (int)b.component.size();
@@ -888,6 +889,11 @@ inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& ga
 	else if (gains.empty()) PANO_HIP_CHECK(op_blend(ctx, &cfg, &g, ims.data(), n, hip_out(cv)));
 	else if (bx > 0) PANO_HIP_CHECK(op_blend_block_gains(ctx, &cfg, &g, ims.data(), n, bx, by, gains.data(), hip_out(cv)));
 	else PANO_HIP_CHECK(op_blend_gains(ctx, &cfg, &g, ims.data(), n, gains.data(), hip_out(cv)));
+	return cv.release();
+}
+template <typename Bundle>
+inline Mat32f hip_blend(const Bundle& b, bool crop, const std::vector<float>& gains, int bx, int by, const float* poly = nullptr) {
+	HipCanvas cv(hip_blend_canvas(b, gains, bx, by, poly));
 	if (crop) hip_crop_in_place(cv);
 	return hip_canvas_to_mat(std::move(cv));
 }
@@ -913,20 +919,58 @@ struct HipCompensation {
 	bool vignetting = false;
 };
 template <typename Bundle>
-inline Mat32f hip_compensate_and_blend(const Bundle& b, const HipCompensation& how, std::vector<float>& gains, std::array<float, 3>& vignette_poly) {
+inline op_canvas* hip_compensate_and_blend_canvas(const Bundle& b, const HipCompensation& how, std::vector<float>& gains, std::array<float, 3>& vignette_poly) {
 	vignette_poly = {0.f, 0.f, 0.f};
 	if (how.vignetting) {
 		if (how.bx * how.by > 1) { fprintf(stderr, "HipStitcher: vignetting and block gains are exclusive\n"); exit(1); }
 		gains = hip_vignette_compensate(b, vignette_poly);
-		return hip_blend(b, false, gains, vignette_poly);
+		return hip_blend_canvas(b, gains, 0, 0, vignette_poly.data());
 	}
-	if (!how.gain) { gains.clear(); return hip_blend(b); }
+	if (!how.gain) { gains.clear(); return hip_blend_canvas(b, gains, 0, 0); }
 	if (how.bx == 1 && how.by == 1) {
 		gains = hip_gain_compensate(b);
-		return hip_blend(b, false, gains);
+		return hip_blend_canvas(b, gains, 0, 0);
 	}
 	gains = hip_gain_compensate_blocks(b, how.bx, how.by);
-	return hip_blend(b, false, gains, how.bx, how.by);
+	return hip_blend_canvas(b, gains, how.bx, how.by);
+}
+template <typename Bundle>
+inline Mat32f hip_compensate_and_blend(const Bundle& b, const HipCompensation& how, std::vector<float>& gains, std::array<float, 3>& vignette_poly) {
+	return hip_canvas_to_mat(HipCanvas(hip_compensate_and_blend_canvas(b, how, gains, vignette_poly)));
+}
+
+// ---- a finished equirectangular panorama looked at again (op_canvas_reproject): planet (main.cc:294-331), a rectilinear view,
+// the faces of a cube.  The canvas stays on the device; the result is a canvas the caller owns, ready for the encoders.
+// hip_pano_frame: where the canvas of a spherical bundle sits on the sphere, or its crop at (x0, y0); wrap is the caller's statement
+// that the columns span exactly one turn.
+template <typename Bundle>
+inline op_pano_frame hip_pano_frame(const Bundle& b, int x0 = 0, int y0 = 0, bool wrap = false) {
+	op_blend_geom g;
+	hip_bundle_geom(b, g);
+	op_pano_frame f;
+	PANO_HIP_CHECK(op_pano_frame_of(&g, x0, y0, &f));
+	f.wrap = wrap ? 1 : 0;
+	return f;
+}
+inline op_canvas* hip_reproject(const op_canvas* canvas, const op_pano_frame& frame, const op_view_spec& spec) {
+	op_canvas* out = nullptr;
+	PANO_HIP_CHECK(op_canvas_reproject(HipContext::get(), canvas, &frame, &spec, &out));
+	return out;
+}
+inline op_view_spec hip_view_look(double yaw, double pitch, double roll, double hfov, int out_w, int out_h) {
+	op_view_spec s;
+	PANO_HIP_CHECK(op_view_look(yaw, pitch, roll, hfov, out_w, out_h, &s));
+	return s;
+}
+inline op_view_spec hip_view_cube_face(int face, int n) {
+	op_view_spec s;
+	PANO_HIP_CHECK(op_view_cube_face(face, n, &s));
+	return s;
+}
+inline op_view_spec hip_view_planet(int n) {
+	op_view_spec s;
+	PANO_HIP_CHECK(op_view_planet(n, &s));
+	return s;
 }
 
 // ---- write_rgb(fname, mat) (lib/imgio.cc:25-41,98-113; main.cc:30,226-233): the file is encoded on the device instead of on one
@@ -1210,6 +1254,11 @@ class HipStitcher : public HipStitcherBase {
 				HipStitcherBase(paths, base_seed, apply_exif_orientation) {}
 
 		Mat32f build() {                                            // stitcher.cc:32-64
+			prepare_blend();
+			const HipCompensation how{gain_compensation, gain_blocks_x, gain_blocks_y, vignetting};
+			return hip_compensate_and_blend(bundle, how, gains, vignette_poly);   // after the homographies are final
+		}
+		void prepare_blend() {                                      // build() up to the blend
 			calc_feature();
 			bundle.views = resident_views || !jpeg_paths.empty() ? feats.views.get() : nullptr;
 			pairwise_matches.assign(imgs.size(), std::vector<MatchInfo>(imgs.size()));
@@ -1220,9 +1269,25 @@ class HipStitcher : public HipStitcherBase {
 			else build_linear_simple();
 			bundle.proj_method = config::ESTIMATE_CAMERA ? ConnectedImages::spherical : ConnectedImages::flat;
 			bundle.update_proj_range();
-			const HipCompensation how{gain_compensation, gain_blocks_x, gain_blocks_y, vignetting};
-			return hip_compensate_and_blend(bundle, how, gains, vignette_poly);   // after the homographies are final
 		}
+
+		// build() with the panorama left on the device (the caller owns the canvas: op_canvas_free), cropped to its largest valid
+		// rectangle under `crop`; hip_write_png / hip_write_jpeg and hip_reproject take it in place
+		op_canvas* build_canvas(bool crop = false) {
+			prepare_blend();
+			const HipCompensation how{gain_compensation, gain_blocks_x, gain_blocks_y, vignetting};
+			HipCanvas cv(hip_compensate_and_blend_canvas(bundle, how, gains, vignette_poly));
+			crop_x0 = crop_y0 = 0;
+			if (crop) {
+				HipCanvas cropped;
+				PANO_HIP_CHECK(op_canvas_crop(HipContext::get(), cv.get(), hip_out(cropped), &crop_x0, &crop_y0));
+				cv = std::move(cropped);
+			}
+			return cv.release();
+		}
+		// where the canvas of the last build_canvas() sits on the sphere (ESTIMATE_CAMERA builds only), its crop origin included
+		int crop_x0 = 0, crop_y0 = 0;
+		op_pano_frame pano_frame(bool wrap = false) const { return hip_pano_frame(bundle, crop_x0, crop_y0, wrap); }
 
 		std::vector<std::vector<MatchInfo>> pairwise_matches;
 		std::vector<Camera> cameras;

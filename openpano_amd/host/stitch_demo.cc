@@ -4,7 +4,7 @@
 //   replaced here by chaining the pairwise homographies to the middle image] -> blend,
 // written with the reference's class and method names.
 //
-//   stitch_demo <in.bin> <out.bin> [base_seed] [camera|camera_ordered|camera_build|cylinder|cylinder_build]
+//   stitch_demo <in.bin> <out.bin> [base_seed] [camera|camera_ordered|camera_build|cylinder|cylinder_build|reproject]
 // ("camera_ordered": ORDERED_INPUT 1 as in BASELINE configs 2-3 -- only (i, i+1 mod n) are matched,
 // Stitcher::linear_pairwise_match, stitcher.cc:115-136; head and tail need not connect.)
 // With "camera" the program runs the ESTIMATE_CAMERA branch of Stitcher::build() instead (BASELINE
@@ -47,12 +47,24 @@
 // --jpeg-orient (anywhere; with --jpeg-list only): every view is turned upright by its file's EXIF orientation, which the
 // reference's decoder ignores (HipStitcher::apply_exif_orientation).  out.bin equals a run on an in.bin that holds the decoded
 // pixels turned beforehand.
+// "reproject": in.bin is a finished equirectangular panorama as this program writes one (int32 H, W ; H*W*3 f32, Color::NO = -1
+// allowed); it goes up once and is looked at again on the device (hip_reproject), as ONE of
+//   --planet N                          the reference's planet (main.cc:294-331) of N x N pixels
+//   --view YAW,PITCH,ROLL,HFOV,WxH      a pinhole view, angles in radians (hip_view_look)
+//   --cube N                            the six faces +x, -x, +y, -y, +z, -z of N x N pixels (hip_view_cube_face)
+// --frame LON0,LAT0,STEP_LON,STEP_LAT says where the panorama sits on the sphere (op_pano_frame; numbers as strtod reads them, hex
+// floats included); without it: square pixels of 2 pi / W, column 0 at -pi, the middle row on the horizon.  --wrap states that the
+// columns span exactly one turn.  out.bin then holds int32 H, W ; H*W*3 f32 per view (six for --cube), and --png / --jpeg name the
+// encoded view; for --cube six files, the face's suffix (_px _nx _py _ny _pz _nz) in front of the extension.
+// The same three options (and --wrap) go with camera_build: the panorama stays on the device (HipStitcher::build_canvas), its frame
+// comes from the bundle (HipStitcher::pano_frame), out.bin ends with the views, and --png / --jpeg name the views, not the panorama.
 // in.bin : int32 n, h, w ; n*h*w*3 float32 (Mat32f layout)
 // out.bin: per image   int32 K ; K*128 f32 ; K*2 f64
 //          int32 npairs ; per pair int32 i, j, M ; M*2 int32 ; int32 ok ; f32 confidence ; 9 f64 ; int32 ninl ; ninl*4 f64
 //          int32 H, W ; H*W*3 f32 (flat-projection linear blend of the chain that connected; H=W=0 if none)
 // tests/test_gpu_host_cpp.py runs it on the GPU box and checks every section against the oracle.
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -77,6 +89,12 @@ struct Options {
 	const char* jpeg_list = nullptr;    // --jpeg-list PATH, --jpeg-orient
 	bool jpeg_orient = false;
 	bool crop = false, profile = false; // --crop, --profile
+	// what to make of the finished panorama: --planet N, --view Y,P,R,HFOV,WxH, --cube N; --wrap, --frame
+	enum View { NO_VIEW, PLANET, LOOK, CUBE } view = NO_VIEW;
+	int view_n = 0, view_w = 0, view_h = 0;
+	double look[4] = {0, 0, 0, 0};
+	bool wrap = false, has_frame = false;
+	double frame[4] = {0, 0, 0, 0};
 };
 
 template <typename T> static void put(FILE* f, const T* p, size_t n) { if (n && fwrite(p, sizeof(T), n, f) != n) { perror("write"); exit(1); } }
@@ -98,6 +116,57 @@ static void put_canvas(FILE* fo, const op_canvas* cv) {
 template <typename Pano> static void write_files(const Options& o, const Pano& pano) {
 	if (o.png_path) hip_write_png(o.png_path, pano);
 	if (o.jpeg_path) hip_write_jpeg(o.jpeg_path, pano, o.jpeg_quality, o.jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
+}
+
+// "out.png" + "_px" -> "out_px.png"
+static std::string with_suffix(const char* path, const char* suffix) {
+	const std::string p(path);
+	const size_t dot = p.rfind('.'), slash = p.rfind('/');
+	if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return p + suffix;
+	return p.substr(0, dot) + suffix + p.substr(dot);
+}
+// the view(s) the options ask for, of the device panorama lying at `frame`: appended to out.bin, encoded into the files
+static void put_views(FILE* fo, const Options& o, const op_canvas* pano, const op_pano_frame& frame) {
+	static const char* const FACE[6] = {"_px", "_nx", "_py", "_ny", "_pz", "_nz"};
+	const int count = o.view == Options::CUBE ? 6 : 1;
+	fprintf(stderr, "Frame: %a %a %a %a %d\n", frame.lon0, frame.lat0, frame.step_lon, frame.step_lat, frame.wrap);
+	for (int k = 0; k < count; ++k) {
+		const op_view_spec spec = o.view == Options::PLANET ? hip_view_planet(o.view_n)
+			: o.view == Options::CUBE ? hip_view_cube_face(k, o.view_n)
+			: hip_view_look(o.look[0], o.look[1], o.look[2], o.look[3], o.view_w, o.view_h);
+		HipCanvas view(hip_reproject(pano, frame, spec));
+		put_canvas(fo, view.get());
+		const char* suffix = o.view == Options::CUBE ? FACE[k] : "";
+		if (o.png_path) hip_write_png(with_suffix(o.png_path, suffix).c_str(), view.get());
+		if (o.jpeg_path) hip_write_jpeg(with_suffix(o.jpeg_path, suffix).c_str(), view.get(), o.jpeg_quality, o.jpeg_444 ? OP_JPEG_444 : OP_JPEG_420);
+		fprintf(stderr, "View %d Size: (%d, %d)\n", k, spec.out_w, spec.out_h);
+	}
+}
+
+// a finished panorama from in.bin, looked at again
+static int run_reproject(const char* in_path, const Options& o) {
+	if (o.view == Options::NO_VIEW) { fprintf(stderr, "reproject wants --planet N, --view YAW,PITCH,ROLL,HFOV,WxH or --cube N\n"); return 2; }
+	FILE* fi = fopen(in_path, "rb");
+	if (!fi) { perror(in_path); return 2; }
+	int32_t hw[2];
+	if (fread(hw, 4, 2, fi) != 2 || hw[0] < 1 || hw[1] < 1) { fprintf(stderr, "%s: no panorama (int32 H, W ; H*W*3 f32)\n", in_path); return 2; }
+	Mat32f pano(hw[0], hw[1], 3);
+	if (fread(pano.ptr(), sizeof(float), (size_t)hw[0] * hw[1] * 3, fi) != (size_t)hw[0] * hw[1] * 3) { fprintf(stderr, "%s: short file\n", in_path); return 2; }
+	fclose(fi);
+	op_pano_frame frame;
+	if (o.has_frame) { frame.lon0 = o.frame[0]; frame.lat0 = o.frame[1]; frame.step_lon = o.frame[2]; frame.step_lat = o.frame[3]; }
+	else {
+		const double step = M_PI * 2 / hw[1];
+		frame.lon0 = -M_PI; frame.step_lon = step; frame.step_lat = step; frame.lat0 = -0.5 * step * (hw[0] - 1);
+	}
+	frame.wrap = o.wrap ? 1 : 0;
+	HipCanvas cv;
+	PANO_HIP_CHECK(op_canvas_upload(HipContext::get(), pano.ptr(), pano.rows(), pano.cols(), hip_out(cv)));
+	FILE* fo = fopen(o.out_path, "wb");
+	if (!fo) { perror(o.out_path); return 2; }
+	put_views(fo, o, cv.get(), frame);
+	fclose(fo);
+	return 0;
 }
 
 static void put_features(FILE* fo, const HipFeatureSet& fs) {
@@ -179,6 +248,17 @@ static int run_build(Stitcher& st, const Options& o) {
 	st.gain_compensation = o.compensation.gain;
 	st.vignetting = o.compensation.vignetting;
 	st.gain_blocks_x = o.compensation.bx; st.gain_blocks_y = o.compensation.by;
+	if (o.view != Options::NO_VIEW) {       // files -> panorama -> view: no pixel of either comes to the host but for out.bin
+		HipCanvas cv(st.build_canvas());
+		FILE* fo = fopen(o.out_path, "wb");
+		if (!fo) { perror(o.out_path); return 2; }
+		put_canvas(fo, cv.get());
+		put(fo, st.gains.data(), st.gains.size());
+		if (st.vignetting) put(fo, st.vignette_poly.data(), 3);
+		put_views(fo, o, cv.get(), st.pano_frame(o.wrap));
+		fclose(fo);
+		return 0;
+	}
 	Mat32f pano = st.build();
 	FILE* fo = fopen(o.out_path, "wb");
 	if (!fo) { perror(o.out_path); return 2; }
@@ -282,6 +362,25 @@ int main(int argc, char** argv) {
 			else if (std::string(argv[k]) == "--jpeg-list" && k + 1 < argc) { o.jpeg_list = argv[++k]; o.resident = true; }
 			else if (std::string(argv[k]) == "--jpeg-orient") o.jpeg_orient = true;
 			else if (std::string(argv[k]) == "--crop") o.crop = true;
+			else if (std::string(argv[k]) == "--wrap") o.wrap = true;
+			else if ((std::string(argv[k]) == "--planet" || std::string(argv[k]) == "--cube") && k + 1 < argc) {
+				if (o.view != Options::NO_VIEW) { fprintf(stderr, "one of --planet, --view, --cube\n"); return 2; }
+				o.view = std::string(argv[k]) == "--planet" ? Options::PLANET : Options::CUBE;
+				if (sscanf(argv[++k], "%d", &o.view_n) != 1 || o.view_n < 1) { fprintf(stderr, "%s wants a size of at least 1; got %s\n", argv[k - 1], argv[k]); return 2; }
+			}
+			else if (std::string(argv[k]) == "--view" && k + 1 < argc) {
+				if (o.view != Options::NO_VIEW) { fprintf(stderr, "one of --planet, --view, --cube\n"); return 2; }
+				o.view = Options::LOOK;
+				if (sscanf(argv[++k], "%lf,%lf,%lf,%lf,%dx%d", &o.look[0], &o.look[1], &o.look[2], &o.look[3], &o.view_w, &o.view_h) != 6) {
+					fprintf(stderr, "--view wants YAW,PITCH,ROLL,HFOV,WxH; got %s\n", argv[k]); return 2;
+				}
+			}
+			else if (std::string(argv[k]) == "--frame" && k + 1 < argc) {
+				if (sscanf(argv[++k], "%lf,%lf,%lf,%lf", &o.frame[0], &o.frame[1], &o.frame[2], &o.frame[3]) != 4) {
+					fprintf(stderr, "--frame wants LON0,LAT0,STEP_LON,STEP_LAT; got %s\n", argv[k]); return 2;
+				}
+				o.has_frame = true;
+			}
 			else if (std::string(argv[k]) == "--profile") o.profile = true;
 			else if (std::string(argv[k]) == "--png" && k + 1 < argc) o.png_path = argv[++k];
 			else if (std::string(argv[k]) == "--jpeg" && k + 1 < argc) o.jpeg_path = argv[++k];
@@ -302,12 +401,16 @@ int main(int argc, char** argv) {
 		argc = m;
 	}
 	if (how.vignetting && how.bx * how.by > 1) { fprintf(stderr, "--vignetting and --gain-blocks are exclusive\n"); return 2; }
-	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build|cylinder|cylinder_build] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH [--jpeg-orient]] [--crop] [--profile]\n", argv[0]); return 2; }
+	if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [base_seed] [camera|camera_ordered|camera_build|cylinder|cylinder_build|reproject] [--gain-compensation] [--gain-blocks BXxBY] [--vignetting] [--png PATH] [--jpeg PATH] [--jpeg-quality Q] [--jpeg-444] [--resident-views] [--jpeg-list PATH [--jpeg-orient]] [--crop] [--profile] [--planet N | --view YAW,PITCH,ROLL,HFOV,WxH | --cube N] [--wrap] [--frame LON0,LAT0,STEP_LON,STEP_LAT]\n", argv[0]); return 2; }
 	if (o.jpeg_orient && !o.jpeg_list) { fprintf(stderr, "--jpeg-orient goes with --jpeg-list\n"); return 2; }
 	o.out_path = argv[2];
 	o.base_seed = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 42u;
 	o.mode = argc > 4 ? argv[4] : "";
 	const std::string& mode = o.mode;
+	if (mode == "reproject") return run_reproject(argv[1], o);
+	if (o.view != Options::NO_VIEW && mode != "camera_build") { fprintf(stderr, "--planet, --view and --cube go with reproject or camera_build\n"); return 2; }
+	if ((o.wrap || o.has_frame) && o.view == Options::NO_VIEW) { fprintf(stderr, "--wrap and --frame go with --planet, --view or --cube\n"); return 2; }
+	if (o.has_frame) { fprintf(stderr, "--frame goes with reproject: a build knows its own frame\n"); return 2; }
 	const bool camera_mode = mode == "camera" || mode == "camera_ordered" || mode == "camera_build";
 	config::ORDERED_INPUT = !camera_mode || mode == "camera_ordered"; config::ESTIMATE_CAMERA = camera_mode; config::TRANS = !camera_mode;   // TRANS mode: affine RANSAC, flat blend
 	config::LAZY_READ = false;
