@@ -185,6 +185,11 @@ int op_debug_set_desc_list_cap(op_ctx* ctx, int floats);
  * classes), and the bytes of returned blocks the pool keeps for reuse.  Any pointer may be NULL.  Exposed so that tests
  * can check that every call gives back what it took, on refusals as well. */
 int op_debug_pool_stats(int64_t* live_blocks, int64_t* live_bytes, int64_t* cached_bytes);
+/* Rows the last op_match_pairs call on ctx that swept anything queued for the exact full scan, forward and reverse
+ * (-1 each before the first such call; a refused call counts: the numbers are what its message reports).  The next call
+ * sizes its exact-scan launches from them.  Either pointer may be NULL.  Read-only; exposed so that tests can check that a
+ * scene queued the rows it was built to queue. */
+int op_debug_match_last_slow(op_ctx* ctx, int* forward_rows, int* reverse_rows);
 
 /* =====================================================================================
  * MATCH -- replaces PairWiseMatcher (feature/matcher.hh:40-67, matcher.cc:73-135) as used by

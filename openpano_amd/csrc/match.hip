@@ -716,6 +716,17 @@ static unsigned slow_grid(int seen) {
 	const long long want = ((long long)seen + seen / 4 + 64 + 7) & ~7LL;
 	return (unsigned)(want < 2048 ? want : 2048);
 }
+// Rows one call may queue for the exact scan, forward and reverse each (a variant build lowers it: tests/test_gpu_match_cases.py)
+#ifndef OP_MATCH_SLOW_CAP
+#define OP_MATCH_SLOW_CAP (1 << 22)
+#endif
+
+int op_debug_match_last_slow(op_ctx* ctx, int* forward_rows, int* reverse_rows) {
+	if (!ctx) OP_FAIL(OP_ERR_INVALID, "op_debug_match_last_slow: NULL context");
+	if (forward_rows) *forward_rows = ctx->match_slow_seen[0];
+	if (reverse_rows) *reverse_rows = ctx->match_slow_seen[1];
+	return OP_OK;
+}
 
 int op_match_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, const int* pairs, int npairs, op_matches** out) {
 	if (!ctx || !cfg || !f || (!pairs && npairs != 0) || npairs < 0 || !out) OP_FAIL(OP_ERR_INVALID, "op_match_pairs: bad argument");
@@ -775,7 +786,7 @@ int op_match_pairs(op_ctx* ctx, const op_config* cfg, const op_features* f, cons
 	for (int i = 0; i < fv.n; ++i)
 		if (fv.counts[i] >= (1 << 22)) OP_FAIL(OP_ERR_CAPACITY, "op_match_pairs: an image with 4 M descriptors or more (the sweep addresses a descriptor set with 32-bit byte offsets)");
 	const size_t nres = (size_t)std::max<long long>(res_rows, 1);
-	const int slow_cap = (int)std::min<long long>(std::max<long long>(res_rows, 1), 1 << 22);
+	const int slow_cap = (int)std::min<long long>(std::max<long long>(res_rows, 1), OP_MATCH_SLOW_CAP);
 
 	// One device arena (the context's grow-only matcher scratch), one memset, one upload per call (every runtime
 	// call costs microseconds).  Layout: a control block of counters -- zero-filled as one range, its head

@@ -132,6 +132,7 @@ PROTOTYPES = {
     "op_debug_set_raw_capacity": (_I, [_V, _I]),
     "op_debug_set_desc_list_cap": (_I, [_V, _I]),
     "op_debug_pool_stats": (_I, [_PI64, _PI64, _PI64]),
+    "op_debug_match_last_slow": (_I, [_V, _PI, _PI]),
     # match
     "op_match_pairs": (_I, [_V, _CFG, _V, _V, _I, _PV]),
     "op_matches_count": (_I, [_V, _I]),
@@ -394,6 +395,13 @@ class Context(_Handle):
     def jpeg_last_rounds(self) -> int:
         """test hook: synchronisation rounds of the last Views.decode_jpeg on this context (op_debug_jpeg_last_rounds)"""
         return lib().op_debug_jpeg_last_rounds(self.handle)
+
+    def match_last_slow(self):
+        """test hook: (forward, reverse) rows the last match_pairs call on this context queued for the exact full scan, (-1, -1)
+        before the first (op_debug_match_last_slow)"""
+        f, r = C.c_int(), C.c_int()
+        check(lib().op_debug_match_last_slow(self.handle, C.byref(f), C.byref(r)))
+        return f.value, r.value
 
     def set_raw_capacity(self, cap: int):
         """test hook: per-image capacity of the speculative raw / refined lists (op_debug_set_raw_capacity)"""
