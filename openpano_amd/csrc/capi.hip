@@ -1,5 +1,5 @@
 // capi.hip -- context, errors, configuration defaults of the C-ABI (include/openpano_hip.h)
-#include "internal.hpp"
+#include "handles.hpp"      // op_ctx_release_workspace
 #include <cstring>
 
 static thread_local std::string g_last_error;

@@ -13,15 +13,11 @@
 // candidates with the reference's exact squared L2 and applies the first ratio test, and a
 // reverse sweep over the survivors only, whose epilogue applies the second test.  MFMA results
 // only RANK candidates; the reference's float arithmetic decides every match.
-#include "internal.hpp"
+#include "handles.hpp"
 #include <cfloat>
 #include <cstring>
 #include <algorithm>
 #include <mutex>
-
-struct op_features;   // sift_host.hip
-struct FeatView { int n; const int* counts; const int64_t* offsets; const float* desc; int device; };
-FeatView op_features_view(const op_features* f);
 
 // The result of a match call stays in HBM: per image pair a (first, second) list sorted by (first, second),
 // pairs back to back in job order.  op_ransac_pairs reads it there; the host only learns the per-pair counts

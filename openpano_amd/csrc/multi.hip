@@ -10,25 +10,11 @@
 // process (the process-per-GPU form with RCCL lives in openpano_amd/distributed.py).  op_match_pairs_multi
 // deals the pair list balanced by K_i * K_j and keeps every device's match lists where they were made;
 // op_ransac_pairs_multi follows the same deal.  Results are identical to the single-device calls, item for item.
-#include "internal.hpp"
+#include "handles.hpp"
 #include <algorithm>
 #include <numeric>
 #include <thread>
 #include <mutex>
-
-struct op_features;
-struct op_matches;
-// sift_host.hip / match.hip internals
-int op_features_allgather_blocks(op_ctx* const* ctxs, int nctx, op_features* const* parts, const int* start, int n, op_features** tables);
-int op_features_replicate(op_ctx* dst, const op_features* f, op_features** out);
-std::vector<op_features*>& op_features_replicas(op_features* f);
-int op_features_device(const op_features* f);
-op_matches* op_matches_merge(op_matches* const* parts, const std::vector<std::vector<int>>& index, int npairs);
-const std::vector<op_matches*>& op_matches_parts(const op_matches* m);
-const std::vector<std::vector<int>>& op_matches_part_index(const op_matches* m);
-int op_matches_num_pairs(const op_matches* m);
-struct op_ransac_result;
-op_ransac_result* op_ransac_merge(op_ransac_result* const* parts, const std::vector<std::vector<int>>& index, int npairs);
 
 struct op_group {
 	std::vector<op_ctx*> ctxs;

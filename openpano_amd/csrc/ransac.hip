@@ -15,26 +15,13 @@
 // base seed and the pair index); the draw sequence is std::mt19937's, with the reference's
 // rejection of repeated indices (:70-77), so a run is reproducible and can be replayed against
 // the CPU path with the same seed.
-#include "internal.hpp"
+#include "handles.hpp"
 #include "ransac_math.hpp"
 #include "ransac_accept.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <omp.h>
-
-struct op_features;
-struct FeatView { int n; const int* counts; const int64_t* offsets; const float* desc; int device; };
-FeatView op_features_view(const op_features* f);
-const double* op_features_coor_device(const op_features* f);
-const double* op_features_coor_host(const op_features* f, op_ctx* ctx);
-struct op_matches;
-int op_matches_num_pairs(const op_matches* m);
-const std::vector<int>& op_matches_counts(const op_matches* m);
-const std::vector<int64_t>& op_matches_offsets(const op_matches* m);
-const std::vector<int>& op_matches_limits(const op_matches* m);
-const int* op_matches_host(const op_matches* m);
-const int* op_matches_device(const op_matches* m, int device, hipStream_t consumer);
 
 using opransac::P2;
 using opaccept::Shape; using opaccept::PointInPolygon; using opaccept::overlap_region; using opaccept::polygon_area; using opaccept::inverse3;

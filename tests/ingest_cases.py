@@ -13,7 +13,7 @@ TR, TC = 24, 72             # its per-workgroup coordinate tables
 
 
 def working_dims(sh, sw, ws):
-    """feature/feature.cc:33-34 as build_plan states it (csrc/sift_host.hip), every step in fp32"""
+    """feature/feature.cc:33-34 as build_plan states it (csrc/sift_plan.cc), every step in fp32"""
     ratio = F(F(ws) * F(2.0)) / F(sw + sh)
     return int(F(sh) * ratio), int(F(sw) * ratio)
 
