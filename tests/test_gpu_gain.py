@@ -116,6 +116,23 @@ def test_overlap_statistics_exact_70_views(ctx, gref):
     assert all(count[hip.pair_index(n, a, b)] > 0 for a, b in ((62, 64), (63, 64), (63, 65)))
 
 
+def test_overlap_statistics_exact_300_permuted_views(ctx, gref):
+    """300 views on a permuted grid (tests/blend_cover_cases.py): the second pass of overlap_walk's marking loop, tiles met by
+    far more images than one chunk holds, and overlapping pairs whose indices lie more than 256 apart"""
+    import blend_cover_cases as bc
+    views, homos, idx = bc.overlap_scene()
+    n = len(views)
+    a, b = bc.pair_arrays(n)
+    for lazy in (0, 1):
+        cfg = _cfg(ESTIMATE_CAMERA=0, TRANS=1, ORDERED_INPUT=1, LAZY_READ=lazy)
+        call = hip.BlendCall(ctx, cfg, views, homos, 0, idx)
+        for stride in (1, 3):
+            count, sums = call.overlap_sums(stride)
+            want_c, want_s = _ref_stats(gref, call, views, cfg, stride)
+            assert np.array_equal(count, want_c) and np.array_equal(sums, want_s), (lazy, stride)
+            assert ((count > 0) & (b - a > 256)).any() and ((count > 0) & (a < 64) & (b >= 64)).any(), (lazy, stride)
+
+
 def test_gains_off_equals_op_blend(ctx):
     """every blend case of test_gpu_blend.py: gains NULL and all-ones gains give op_blend's canvas bit for bit"""
     from test_gpu_blend import CASES, _cfg as blend_cfg

@@ -156,6 +156,25 @@ def test_block_statistics_exact_70_views(ctx, gref):
     assert all(count[hip.pair_index(n, a, b)].sum() > 0 for a, b in ((62, 64), (63, 64), (63, 65)))
 
 
+def test_block_statistics_exact_300_permuted_views(ctx, gref):
+    """300 views on a permuted grid (tests/blend_cover_cases.py), 2 x 2 blocks: the second pass of overlap_walk's marking
+    loop, tiles met by far more images than one chunk holds, and overlapping pairs whose indices lie more than 256 apart"""
+    import blend_cover_cases as bc
+    views, homos, idx = bc.overlap_scene()
+    n = len(views)
+    a, b = bc.pair_arrays(n)
+    cfg = _flat_cfg()
+    call = hip.BlendCall(ctx, cfg, views, homos, 0, idx)
+    for stride in (1, 3):
+        count, sums = call.block_overlap_sums(2, 2, stride)
+        want_c, want_s = ref_block_stats(gref, call, views, cfg, stride, 2, 2)
+        assert np.array_equal(count, want_c) and np.array_equal(sums, want_s), stride
+        some = count.sum(axis=(1, 2)) > 0
+        assert (some & (b - a > 256)).any() and (some & (a < 64) & (b >= 64)).any(), stride
+        # neighbours lie 5, 10 pixels apart, a block is 6 x 5: a shared pixel falls into different blocks of the two views
+        assert (count.sum(axis=0)[~np.eye(4, dtype=bool)] > 0).all()
+
+
 @pytest.mark.parametrize("proj,method", [("flat", 0), ("camera", 1), ("camera", 2)])
 @pytest.mark.parametrize("lazy", [0, 1])
 def test_one_by_one_reduces_to_per_image(ctx, proj, method, lazy):

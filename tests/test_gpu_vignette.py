@@ -146,6 +146,28 @@ def test_statistics_exact_70_views(ctx, vref):
     assert all(count[hip.pair_index(n, a, b)] > 0 for a, b in ((62, 64), (63, 64), (63, 65)))
 
 
+def test_statistics_exact_300_permuted_views(ctx, vref):
+    """300 views on a permuted grid (tests/blend_cover_cases.py): the second pass of overlap_walk's marking loop, tiles met by
+    far more images than one chunk holds, and overlapping pairs whose indices lie more than 256 apart"""
+    import blend_cover_cases as bc
+    views, homos, idx = bc.overlap_scene()
+    n = len(views)
+    a, b = bc.pair_arrays(n)
+    cfg = _flat_cfg()
+    call = hip.BlendCall(ctx, cfg, views, homos, 0, idx)
+    for stride in (1, 3):
+        full = None
+        for clip in (1.0, 0.6):
+            count, mom = call.vignette_overlap_sums(stride, clip)
+            want_c, want_m = ref_stats(vref, call, views, cfg, stride, clip)
+            assert np.array_equal(count, want_c) and np.array_equal(mom, want_m), (stride, clip)
+            assert ((count > 0) & (b - a > 256)).any() and ((count > 0) & (a < 64) & (b >= 64)).any(), (stride, clip)
+            if full is None:
+                full = count
+            else:
+                assert 0 < count.sum() < full.sum()            # clip 0.6 drops samples
+
+
 def test_zero_curve_is_plain_gains(ctx):
     """every blend case of test_gpu_blend.py: a = 0 gives op_blend_gains(g)'s canvas bit for bit; a = 0 with g = 1 (and NULL
     gains and curve) op_blend's"""
